@@ -12,7 +12,14 @@ uint32).  --scaling strong (default): the 8 containers are dealt 
 "8 GiB at 1/2/4/8 GPUs".  --scaling weak: every rank gets its own 8 containers.
 --workload dickens_like|mozilla_like|spamfile_like times one file of BASELINE configs[2]/[3] on one GPU instead.
 
+A plain run sets up, warms up, times the K steps, checks that the last step round-tripped bit for bit and prints the ONE JSON
+line.  --full adds everything beside the headline: the pre-verification round trip, per-kernel times and the roofline,
+the second timed region with the block index walked from the streams alone, the index walk times and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs), so that two builds can be compared.
+
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs bench_outputs
   python bench.py --gpus N --steps K --warmup W          (no launcher: starts its own N ranks, one per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
@@ -29,11 +36,13 @@ for _p in (os.path.join(ROOT, "pim-compression_amd"), os.path.join(ROOT, "tests"
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec peak
 METRIC = "end-to-end GB/s (compress + decompress) on Silesia-mix; bit-exact ratio parity"
 BLOCK_SIZE = 32768              # reference default, snappy/dpu_snappy.c:100
 TOTAL_CONTAINERS = 8            # the 8 GiB batch: 8 x 1 GiB
 STREAM_DESC_BYTES = 48          # sizeof(snappy_hip_stream_desc)
+DUMP_SAMPLE = 1 << 22           # --dump-outputs: elements sampled from each large output (float32: 16 MB each)
+DUMP_SEED = 20261016
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -452,6 +461,105 @@ def load_pmc_traffic():
         return None
 
 
+def sample_elements(pieces, k, seed):
+    """Elements of the concatenation of `pieces` ((tensor, length) pairs, any device) at k positions drawn with `seed`, in
+    order -- every element when there are at most k -- as float32 (exact for bytes and block status words)."""
+    import numpy as np
+    import torch
+    lens = np.array([ln for _, ln in pieces], dtype=np.int64)
+    total = int(lens.sum())
+    if total <= k:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(seed).integers(0, total, size=k, dtype=np.int64))
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    out = [np.zeros(0, dtype=np.float32)]
+    for j, (t, _) in enumerate(pieces):
+        lo, hi = np.searchsorted(pos, starts[j]), np.searchsorted(pos, starts[j + 1])
+        if hi > lo:
+            idx = torch.from_numpy(pos[lo:hi] - starts[j]).to(t.device)
+            out.append(t[idx].cpu().numpy().astype(np.float32))
+    return np.concatenate(out)
+
+
+def dump_outputs(batch, out_dir, rank=0, world=1):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy (DIR/<name>_rank<r>.npy from every
+    rank of a multi-rank job).  The inputs depend on the arguments alone, so two builds run with the same arguments can be
+    compared file by file:
+      stream_lengths       float64, the length of every container's framed stream;
+      compressed_sample    float32, bytes of the framed streams, concatenated in container order, at DUMP_SAMPLE positions
+                           drawn with a fixed seed, in order (every byte when the streams are shorter);
+      decompressed_sample  float32, the same for the decoded plaintexts;
+      block_status         float32, the decoder's status of every block (0 = OK), sampled the same way past DUMP_SAMPLE blocks.
+    At most 3 x DUMP_SAMPLE float32 over all ranks (48 MB) plus the lengths."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    k = max(1, DUMP_SAMPLE // world)
+    arrays = {
+        "stream_lengths": np.array(batch.stream_lens, dtype=np.float64),
+        "compressed_sample": sample_elements(list(zip(batch.streams, batch.stream_lens)), k, DUMP_SEED),
+        "decompressed_sample": sample_elements(list(zip(batch.outs, batch.n)), k, DUMP_SEED + 1),
+        "block_status": sample_elements(list(zip(batch.status, batch.nb)), k, DUMP_SEED + 2),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, (name if world == 1 else f"{name}_rank{rank}") + ".npy"), a)
+
+
+def full_figures(batch, tot_bytes, secs_alone, steps):
+    """--full: the keys of the result line beside the headline -- per-kernel times from the timed steps' HIP events, the
+    second timed region (streams alone), the index walk times of container 0 and the roofline."""
+    c_ms = batch.kernel_ms("compress")
+    d_ms = batch.kernel_ms("decompress")
+    launches = max(1, batch.groups)                       # K1 / K2 launches per step (equal groups of containers)
+    u = sum(batch.n) / launches                           # uncompressed bytes per launch
+    c = sum(batch.stream_lens) / launches
+    algo_bytes = u + c                                    # read plaintext once, write compressed once
+    achieved = algo_bytes / (c_ms * 1e-3) / 1e9
+    d_algo = u + c
+    pmc = load_pmc_traffic()
+    share = batch.lds_share()
+    traffic = None
+    if pmc and "k1_global_table_bytes_per_input_byte" in pmc:
+        # rocprofv3 --pmc serialises the co-running K1 kernels, so HBM bytes were measured for each form running
+        # alone and are combined here with the block share the LDS-table form actually took
+        traffic = int(u * ((1.0 - share) * pmc["k1_global_table_bytes_per_input_byte"] +
+                           share * pmc["k1_lds_table_bytes_per_input_byte"]))
+    return {
+        "compress_kernel_GBps": round(u / (c_ms * 1e-3) / 1e9, 3),
+        "decompress_kernel_GBps": round(u / (d_ms * 1e-3) / 1e9, 3),
+        # the same steps with the block index taken from the streams alone: ONE snappy_hip_index_streams launch walks the
+        # size chains of all the rank's streams inside the step (snappy_decompress.c:306-341), nothing but the framed
+        # streams crosses from the compressor to the decoder
+        "value_from_stream_alone": round(tot_bytes / secs_alone / 1e9, 4) if secs_alone else None,
+        "ms_per_step_from_stream_alone": round(secs_alone / steps * 1e3, 3) if secs_alone else None,
+        "index": {"mode": "value: the compressor's offsets verified against the size chain, every link in parallel "
+                          "(snappy_hip_verify_index); value_from_stream_alone: the chain found on the device from the "
+                          "stream's bytes alone, all streams of the rank in one call (snappy_hip_index_streams: 256 "
+                          "walkers per stream over segments of the chain, laid end to end iff every segment ends exactly "
+                          "on the next one's start; the serial walk for any stream that leaves unresolved)",
+                  "fallback_serial_walks": batch.fallback_walks,
+                  "index_ms_container0": round(batch.walk_ms(), 3),
+                  "serial_walk_ms_container0": round(batch.walk_ms(serial=True), 3)},
+        "roofline": {"bound": "hbm", "kernel": "K1 = compress_blocks_global_table_kernel + compress_blocks_lds_table_kernel "
+                                               "(co-running pair, one launch over the rank's containers)",
+                     "achieved": round(achieved, 3),
+                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6),
+                     "traffic": traffic,
+                     "traffic_source": "profiles/pmc_traffic.json (offline rocprofv3 --pmc FETCH_SIZE + WRITE_SIZE of each K1 "
+                                       "form alone, bytes per input byte) x this run's block share of the two forms",
+                     "lds_table_block_share": round(share, 4),
+                     # what the kernel IS bound by (offline counter passes, like `traffic`): instruction issue, not HBM bytes
+                     "issue": (pmc or {}).get("k1_issue"),
+                     "algorithmic_bytes_per_launch": int(algo_bytes), "avg_launch_ms": round(c_ms, 4),
+                     "decompress_kernel": {"achieved": round(d_algo / (d_ms * 1e-3) / 1e9, 3),
+                                           "frac": round(d_algo / (d_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 6),
+                                           "traffic": int(u * pmc["k2_bytes_per_output_byte"])
+                                           if pmc and "k2_bytes_per_output_byte" in pmc else None,
+                                           "algorithmic_bytes_per_launch": int(d_algo),
+                                           "avg_launch_ms": round(d_ms, 4)}},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -468,14 +576,23 @@ def main():
     ap.add_argument("--groups", type=int, default=1,
                     help="launch groups per step: the decode of group g runs on a second stream underneath the compression of "
                          "group g+1 (1 = strictly compress-all then decompress-all)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the pre-verification round trip, per-kernel "
+                         "times and the roofline, the second timed region from the streams alone, the index walk times and "
+                         "the CPU baseline (the --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-stream-alone", action="store_true",
-                    help="skip the second timed region (the same steps with the block index walked from the streams alone)")
+                    help="with --full: skip the second timed region (the same steps with the block index walked from the streams "
+                         "alone)")
     ap.add_argument("--no-preverify", action="store_true",
-                    help="skip the extra round trip through the serial size-chain walk before the timed steps (its per-container "
-                         "launches would mix with the batched ones in a rocprofv3 --stats average); the timed path itself is "
-                         "still checked bit for bit after the last step")
+                    help="with --full: skip the extra round trip through the serial size-chain walk before the timed steps (its "
+                         "per-container launches would mix with the batched ones in a rocprofv3 --stats average); the timed "
+                         "path itself is still checked bit for bit after the last step")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # N > 1 without a launcher: start the N ranks from here (before anything touches the GPU) and relay rank 0's line
     if args.gpus > 1 and not launched_by_a_launcher():
@@ -511,8 +628,9 @@ def main():
     n = args.container_mib << 20
     plan = [0] if single_file else shard_plan(rank, world, args.containers, args.scaling)
     batch = Batch(shb, torch, build_inputs(shb, torch, args.workload, plan, n), groups=args.groups)
-    ok = True if args.no_preverify else batch.verify()
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and batch.count
+    full = args.full
+    ok = batch.verify() if full and not args.no_preverify else True
+    want_cpu = full and rank == 0 and world == 1 and not args.no_cpu_baseline and batch.count
 
     for _ in range(args.warmup):
         batch.step()
@@ -529,14 +647,16 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        batch.step(record=True)
+        batch.step(record=full)                                   # per-kernel HIP events only for --full's figures
     fence()
     elapsed = time.perf_counter() - t0
     ok = ok and batch.verify_last_step()
+    if args.dump_outputs:
+        dump_outputs(batch, args.dump_outputs, rank, world)
     # ---- the same K steps with a decoder that starts from the streams alone (its own timed region, reported beside `value`):
     #      the block index comes from snappy_hip_index_streams inside the step ----
     elapsed_alone = None
-    if not args.no_stream_alone:
+    if full and not args.no_stream_alone:
         batch.step(stream_alone=True)
         fence()
         t0 = time.perf_counter()
@@ -559,22 +679,6 @@ def main():
                                           device="cuda" if backend == "nccl" else "cpu")
 
     if rank == 0:
-        c_ms = batch.kernel_ms("compress")
-        d_ms = batch.kernel_ms("decompress")
-        launches = max(1, batch.groups)                       # K1 / K2 launches per step (equal groups of containers)
-        u = sum(batch.n) / launches                           # uncompressed bytes per launch
-        c = sum(batch.stream_lens) / launches
-        algo_bytes = u + c                                    # read plaintext once, write compressed once
-        achieved = algo_bytes / (c_ms * 1e-3) / 1e9
-        d_algo = u + c
-        pmc = load_pmc_traffic()
-        share = batch.lds_share()
-        traffic = None
-        if pmc and "k1_global_table_bytes_per_input_byte" in pmc:
-            # rocprofv3 --pmc serialises the co-running K1 kernels, so HBM bytes were measured for each form running
-            # alone and are combined here with the block share the LDS-table form actually took
-            traffic = int(u * ((1.0 - share) * pmc["k1_global_table_bytes_per_input_byte"] +
-                               share * pmc["k1_lds_table_bytes_per_input_byte"]))
         if single_file:
             workload = (f"{args.workload} {batch.n[0]} B (stand-in for BASELINE configs[2]/[3], "
                         f"pim-compression_amd/standins.py), block_size {BLOCK_SIZE}")
@@ -600,39 +704,9 @@ def main():
                        "parallelism": f"whole containers dealt over {world} GPU(s), no collective"},
             "roundtrip_bit_exact": bool(ok),
             "space_saving": round(1.0 - tot_comp / tot_bytes, 6),
-            "compress_kernel_GBps": round(u / (c_ms * 1e-3) / 1e9, 3),
-            "decompress_kernel_GBps": round(u / (d_ms * 1e-3) / 1e9, 3),
-            # the same steps with the block index taken from the streams alone: ONE snappy_hip_index_streams launch walks the
-            # size chains of all the rank's streams inside the step (snappy_decompress.c:306-341), nothing but the framed
-            # streams crosses from the compressor to the decoder
-            "value_from_stream_alone": round(tot_bytes / secs_alone / 1e9, 4) if secs_alone else None,
-            "ms_per_step_from_stream_alone": round(secs_alone / args.steps * 1e3, 3) if secs_alone else None,
-            "index": {"mode": "value: the compressor's offsets verified against the size chain, every link in parallel "
-                              "(snappy_hip_verify_index); value_from_stream_alone: the chain found on the device from the "
-                              "stream's bytes alone, all streams of the rank in one call (snappy_hip_index_streams: 256 "
-                              "walkers per stream over segments of the chain, laid end to end iff every segment ends exactly "
-                              "on the next one's start; the serial walk for any stream that leaves unresolved)",
-                      "fallback_serial_walks": batch.fallback_walks,
-                      "index_ms_container0": round(batch.walk_ms(), 3),
-                      "serial_walk_ms_container0": round(batch.walk_ms(serial=True), 3)},
-            "roofline": {"bound": "hbm", "kernel": "K1 = compress_blocks_global_table_kernel + compress_blocks_lds_table_kernel "
-                                                   "(co-running pair, one launch over the rank's containers)",
-                         "achieved": round(achieved, 3),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6),
-                         "traffic": traffic,
-                         "traffic_source": "profiles/pmc_traffic.json (offline rocprofv3 --pmc FETCH_SIZE + WRITE_SIZE of each K1 "
-                                           "form alone, bytes per input byte) x this run's block share of the two forms",
-                         "lds_table_block_share": round(share, 4),
-                         # what the kernel IS bound by (offline counter passes, like `traffic`): instruction issue, not HBM bytes
-                         "issue": (pmc or {}).get("k1_issue"),
-                         "algorithmic_bytes_per_launch": int(algo_bytes), "avg_launch_ms": round(c_ms, 4),
-                         "decompress_kernel": {"achieved": round(d_algo / (d_ms * 1e-3) / 1e9, 3),
-                                               "frac": round(d_algo / (d_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 6),
-                                               "traffic": int(u * pmc["k2_bytes_per_output_byte"])
-                                               if pmc and "k2_bytes_per_output_byte" in pmc else None,
-                                               "algorithmic_bytes_per_launch": int(d_algo),
-                                               "avg_launch_ms": round(d_ms, 4)}},
         }
+        if full:
+            line.update(full_figures(batch, tot_bytes, secs_alone, args.steps))
         if want_cpu:
             line["cpu_baseline"] = cpu_baseline(batch, torch, gpu_stream0)
         print(json.dumps(line), flush=True)

@@ -26,7 +26,7 @@ def _run(cmd, env=None):
 
 
 def test_bench_json_line_keeps_the_contract():
-    d = _run([sys.executable, "bench.py", "--containers", "2", "--container-mib", "64", "--steps", "2", "--warmup", "1"])
+    d = _run([sys.executable, "bench.py", "--containers", "2", "--container-mib", "64", "--steps", "2", "--warmup", "1", "--full"])
     assert REQUIRED <= set(d), REQUIRED - set(d)
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         assert d["metric"] == json.load(f)["metric"]
@@ -45,6 +45,34 @@ def test_bench_json_line_keeps_the_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "GB/s" and c["value"] > 0 and c["cores"] >= 1 and c["sample"]
     assert c["gpu_stream_equals_oracle_stream"] is True
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the line holds the headline alone, --steps sets the timed steps, and --dump-outputs writes the last
+    step's outputs as float .npy files that two runs with the same arguments reproduce exactly."""
+    import numpy as np
+    args = [sys.executable, "bench.py", "--containers", "2", "--container-mib", "64", "--steps", "3", "--warmup", "1"]
+    d = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert not (REQUIRED - {"roofline", "cpu_baseline"}) - set(d)
+    assert not {"roofline", "cpu_baseline", "value_from_stream_alone", "index", "compress_kernel_GBps"} & set(d)
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        assert d["metric"] == json.load(f)["metric"]
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["roundtrip_bit_exact"] is True
+    assert abs(d["value"] - 2 * 64 * 2**20 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.02 * d["value"]
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["block_status.npy", "compressed_sample.npy", "decompressed_sample.npy", "stream_lengths.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64) and a[n].size > 0
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / n)), n
+    assert a["stream_lengths.npy"].shape == (2,) and 0 < a["stream_lengths.npy"].sum() < 2 * 64 * 2**20
+    assert a["block_status.npy"].shape == (2 * 2048,) and not a["block_status.npy"].any()
+    for n in ("compressed_sample.npy", "decompressed_sample.npy"):
+        assert a[n].min() >= 0 and a[n].max() <= 255 and np.array_equal(a[n], np.round(a[n]))
 
 
 def test_bench_two_ranks_on_one_device():

@@ -14,7 +14,7 @@ for rep in 1 2; do
     cp pim-compression_amd/libab_$i.so pim-compression_amd/libsnappy_hip.so
     for w in dickens_like mozilla_like spamfile_like silesia_mix; do
       echo -n "[$d] $w "
-      timeout -k 10 300 python3 bench.py --workload $w --steps $([ $w = silesia_mix ] && echo 4 || echo 40) --warmup $([ $w = silesia_mix ] && echo 1 || echo 5) --no-cpu-baseline --no-preverify --no-stream-alone 2>/dev/null | python3 -c "
+      timeout -k 10 300 python3 bench.py --workload $w --steps $([ $w = silesia_mix ] && echo 4 || echo 40) --warmup $([ $w = silesia_mix ] && echo 1 || echo 5) --full --no-cpu-baseline --no-preverify --no-stream-alone 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('ms/step %.3f  K1 %.3f ms  K2 %.3f ms ok %s' % (d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['decompress_kernel']['avg_launch_ms'], d['roundtrip_bit_exact']))"
