@@ -1,0 +1,681 @@
+// dropin_pair.hpp -- snappy_compress_gpu / snappy_decompress_gpu on host buffers (reference L2 signatures), included at
+// the end of snappy_hip.hip.  Where the bytes go is csrc/dropin_plan.hpp; this file only issues the HIP work.
+
+namespace {   // (C++ linkage: an unnamed namespace inside extern "C" would still export unmangled names)
+
+// The compress pipeline keeps six streams busy at once (copy-in, two K1 launches, the LDS-table helper, framing,
+// copy-out).  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams on
+// one queue run in enqueue order: measured here, the copy-in of chunk k+1 then waits for the K1 launch of chunk k and the
+// pipeline degenerates to the phased form (38 instead of 52 GB/s on a 3 GiB input).  The library does NOT touch the
+// process environment: a host program that wants the overlap exports GPU_MAX_HW_QUEUES=8 before its first HIP call (the
+// CLI and the Python binding do); without it only the overlap is lost, never bytes.
+
+// Streams of one shard's pipeline.  Creating a stream costs milliseconds (a hardware queue each), so the sets are made
+// once per process and shard index and kept: a long-lived caller pays for them in its first call only.
+struct PipelineStreams {
+    hipStream_t in = nullptr, run = nullptr, run2 = nullptr, post = nullptr, out = nullptr;
+    hipEvent_t start = nullptr;
+    uint64_t* h_len = nullptr;          // page-locked scratch: stream length per chunk / block offsets
+    size_t h_len_count = 0;
+};
+
+// The cached streams and their page-locked scratch are per process, so overlapped calls from several host threads take
+// turns (the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618).
+std::mutex* pipeline_mutex()
+{
+    static std::mutex* m = new std::mutex;
+    return m;
+}
+
+// Cached per (device, shard): streams, events and the DMA queues behind them belong to the device they were created on, and
+// the shard-to-device mapping follows the caller's current device (ShardDevices), so shard g of one call and shard g of the
+// next may run on different devices; two shards on ONE device (SNAPPY_HIP_OVERSUBSCRIBE) run in different host threads at
+// the same time and must not share a set either.
+int pipeline_streams(int device, int shard, size_t chunks, PipelineStreams* out)
+{
+    static std::map<int, PipelineStreams*> cache;
+    static std::mutex cache_mutex;
+    if (shard < 0 || shard >= 64 || device < 0 || device >= 64) return fail(SNAPPY_HIP_ERR_ARG, "shard / device index out of range");
+    PipelineStreams* pp = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(cache_mutex);
+        PipelineStreams*& slot = cache[pipeline_stream_key(device, shard)];
+        if (!slot) slot = new PipelineStreams;               // never destroyed (threads may outlive statics)
+        pp = slot;
+    }
+    PipelineStreams& p = *pp;                            // one (device, shard) is only ever touched by the host thread driving that shard
+    if (!p.in) {
+        HIP_TRY(hipStreamCreateWithFlags(&p.in, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&p.run, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&p.run2, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&p.post, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&p.out, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreate(&p.start));
+        // a stream gets its hardware queue at first use: use each one now, in the load phase, not under the first chunk
+        for (hipStream_t st : {p.in, p.run, p.run2, p.post, p.out}) {
+            WorkCounter c;
+            if (int rc = next_work_counter(&c, st)) return rc;
+            if (int rc = work_counter_launched(c, st)) return rc;
+        }
+        // ... and the first asynchronous copy in either direction on a stream starts a DMA queue of its own (~8 ms)
+        const size_t n = 256u << 10;
+        void *h = nullptr, *d = nullptr;
+        HIP_TRY(hipHostMalloc(&h, n, hipHostMallocPortable));
+        HIP_TRY(hipMalloc(&d, n));
+        memset(h, 0, n);
+        HIP_TRY(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, p.in));
+        HIP_TRY(hipStreamSynchronize(p.in));
+        for (hipStream_t st : {p.out, p.post, p.run, p.run2}) HIP_TRY(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(d);
+        (void)hipHostFree(h);
+    }
+    if (chunks > p.h_len_count) {
+        if (p.h_len) (void)hipHostFree(p.h_len);
+        p.h_len = nullptr;
+        p.h_len_count = 0;
+        const size_t want = std::max<size_t>(chunks, 64);
+        HIP_TRY(hipHostMalloc((void**)&p.h_len, want * sizeof(uint64_t), hipHostMallocPortable));
+        p.h_len_count = want;
+    }
+    *out = p;
+    return 0;
+}
+
+// A shard of either direction: its range, streams and timings, and what it holds on its device -- allocations and
+// per-chunk events, recorded as they are made and given back by release().
+struct ShardBase : dropin_plan::Range {
+    ShardBase(const dropin_plan::Range& r) : dropin_plan::Range(r) {}
+    PipelineStreams ps;
+    float kernel_ms = 0.f, exposed_in_ms = 0.f;
+    std::vector<void*> mem;
+    std::vector<hipEvent_t> events;
+
+    template <class T>
+    hipError_t alloc(T** p, uint64_t bytes)
+    {
+        const hipError_t e = hipMalloc((void**)p, bytes);
+        if (e == hipSuccess) mem.push_back(*p);
+        return e;
+    }
+    hipError_t event(hipEvent_t* ev)
+    {
+        const hipError_t e = hipEventCreate(ev);
+        if (e == hipSuccess) events.push_back(*ev);
+        return e;
+    }
+    // device memory and per-chunk events (the cached streams stay); safe to call twice
+    void release()
+    {
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (void* p : mem) (void)hipFree(p);
+        events.clear();
+        mem.clear();
+    }
+};
+
+struct CompressChunk : dropin_plan::CompressChunk {
+    CompressChunk(const dropin_plan::CompressChunk& p) : dropin_plan::CompressChunk(p) {}
+    uint64_t stream_len = 0, out_off = 0;       // this chunk's framed stream, and where its blocks go in the output
+    hipEvent_t ev_in = nullptr, ev_k1 = nullptr, ev_run = nullptr;
+};
+
+struct CompressShard : ShardBase {
+    using ShardBase::ShardBase;
+    uint8_t *d_in = nullptr, *d_slots = nullptr, *d_stream = nullptr, *d_offsets = nullptr;    // (d_stream, d_offsets: the pools)
+    uint32_t* d_bytes = nullptr;
+    uint64_t* d_stream_len = nullptr;
+    void* d_scratch[2] = {};                    // one per K1 stream
+    uint64_t scratch_bytes = 0;                 // sized for this shard's device
+    std::vector<CompressChunk> chunks;          // one chunk = the phased form
+};
+
+struct DecompressChunk : dropin_plan::Range {
+    DecompressChunk(const dropin_plan::Range& r) : dropin_plan::Range(r) {}
+    hipEvent_t ev_in = nullptr, ev_run = nullptr;
+};
+
+struct DecompressShard : ShardBase {
+    using ShardBase::ShardBase;
+    uint64_t in_off = 0, in_len = 0;            // slice of the compressed stream (relative to input->buffer)
+    uint8_t *d_stream = nullptr, *d_out = nullptr;
+    uint64_t* d_boff = nullptr;
+    uint32_t* d_status = nullptr;
+    bool bad = false, bad_chain = false;
+    std::vector<DecompressChunk> chunks;        // one chunk = the phased form
+    // size chain of the shard (snappy_decompress.c:317-340), walked on demand: blocks [0, walk.block) have their offsets
+    // (relative to in_off) in ps.h_len[], [walk.block] holds the end of the last one; walk.at = its stream position
+    dropin_plan::Walk walk;
+};
+
+// Error returns leave through this: drain every device a shard used, then give its memory back (the normal path has
+// released everything in its timed "free" phase by then, and release() is idempotent).
+template <class Shard>
+struct ShardCleanup {
+    std::vector<Shard>& shards;
+    const ShardDevices& devs;
+    ~ShardCleanup()
+    {
+        for (size_t g = 0; g < shards.size(); ++g) {
+            if (shards[g].mem.empty() && shards[g].events.empty()) continue;
+            if (hipSetDevice(devs.device_of((int)g)) == hipSuccess) (void)hipDeviceSynchronize();
+            shards[g].release();
+        }
+    }
+};
+
+snappy_status report(const char* where)
+{
+    fprintf(stderr, "snappy_hip: %s failed: %s\n", where, g_last_error.c_str());
+    return SNAPPY_INVALID_INPUT;   // the reference maps a failed launch to this (snappy_compress.c:618-623)
+}
+
+// fn(shard, g) on the device of every non-empty shard (of every shard with `all`), one host thread per shard
+template <class Shard, class Fn>
+int on_shards(std::vector<Shard>& sh, const ShardDevices& devs, Fn fn, bool all = false)
+{
+    return for_each_device((int)sh.size(), [&](int g) -> int {
+        HIP_TRY(hipSetDevice(devs.device_of(g)));
+        return (all || sh[g].num_blocks) ? fn(sh[g], g) : 0;
+    });
+}
+
+// one timed phase (dpu_alloc / dpu_load / dpu_free): its seconds go to *seconds, a failure becomes report(where)
+template <class Shard, class Fn>
+snappy_status timed_phase(std::vector<Shard>& sh, const ShardDevices& devs, double* seconds, const char* where, Fn fn, bool all = false)
+{
+    const double t0 = now_seconds();
+    const int rc = on_shards(sh, devs, fn, all);
+    *seconds = now_seconds() - t0;
+    return rc ? report(where) : SNAPPY_OK;
+}
+
+// "load" phase (dpu_load, snappy_compress.c:541): make the device ready so that the copy and run phases measure
+// copies and kernels -- code object on the device, copy engines and the co-run helper stream initialised.
+int warm_up_device()
+{
+    hipFuncAttributes fa;
+    // (the default K1 launch for blocks of more than 8 KiB: the cached global-table kernel and the LDS-table kernel, stream form)
+    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::compress_blocks_global_table_kernel<64, 3, 1, 512>)));
+    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::compress_blocks_lds_table_kernel<64, 3>)));
+    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::gather_slots_kernel)));
+    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::decompress_blocks_kernel)));
+    CoRunResources* cr = nullptr;
+    if (int rc = corun_resources(&cr)) return rc;
+    WorkCounter c;
+    if (int rc = next_work_counter(&c, nullptr)) return rc;      // also touches the module's globals
+    uint32_t probe = 0;
+    HIP_TRY(hipMemcpy(&probe, c.ptr, sizeof(probe), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c.ptr, &probe, sizeof(probe), hipMemcpyHostToDevice));
+    if (int rc = work_counter_launched(c, nullptr)) return rc;
+    // the first copy of more than a few KiB in either direction starts the DMA engines (~8 ms, once per process)
+    static std::mutex engines_mutex;
+    static bool engines_started[64] = {};                        // per process and device, not per (short-lived) shard thread
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> engines_lock(engines_mutex);
+    if (dev >= 0 && dev < 64 && !engines_started[dev]) {
+        const size_t n = 1u << 20;
+        void *h = nullptr, *d = nullptr;
+        HIP_TRY(hipHostMalloc(&h, n, hipHostMallocPortable));
+        HIP_TRY(hipMalloc(&d, n));
+        memset(h, 0, n);
+        HIP_TRY(hipMemcpy(d, h, n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h, d, n, hipMemcpyDeviceToHost));
+        (void)hipFree(d);
+        (void)hipHostFree(h);
+        engines_started[dev] = true;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return 0;
+}
+
+// The end of either direction.  copy_in / run = the slowest shard's exposed copy-in and kernel time (the shards run side
+// by side); copy_out = the rest of the section's wall time.  Then the per-tasklet log lines (dpu-compress/dpu_task.c:88)
+// and the timed free (dpu_free, :707).
+template <class Shard, class InBytes>
+snappy_status finish_shards(std::vector<Shard>& sh, const ShardDevices& devs, struct program_runtime* runtime, double wall,
+                            InBytes in_bytes)
+{
+    float in_ms = 0.f, run_ms = 0.f;
+    for (const Shard& s : sh) {
+        in_ms = std::max(in_ms, s.exposed_in_ms);
+        run_ms = std::max(run_ms, s.kernel_ms);
+    }
+    runtime->copy_in = in_ms / 1000.0;
+    runtime->run = run_ms / 1000.0;
+    runtime->copy_out = std::max(0.0, wall - runtime->copy_in - runtime->run);
+    for (size_t g = 0; g < sh.size(); ++g)
+        printf("GPU %d: %f s, %lu bytes\n", (int)g, sh[g].kernel_ms / 1000.0, (unsigned long)in_bytes(sh[g]));
+    return timed_phase(sh, devs, &runtime->d_free, "free", [](Shard& s, int) -> int {
+        s.release();
+        return 0;
+    });
+}
+
+// The drop-in pair's device side (phases of snappy_compress.c:528-709 / snappy_decompress.c:306-493), overlapped per
+// chunk k+1 is copied in while chunk k is compressed / decoded and chunk k-1 is framed and
+// copied out, on separate streams; one chunk per shard IS the reference's phased order.  Chunks are whole blocks and the
+// host concatenates chunk streams like per-device streams, so the bytes do not depend on the chunking.  The enqueue order
+// (kernels of k, copy-in of k+1, copy-out of k-1) keeps the overlap when the caller's buffers are pageable and
+// hipMemcpyAsync degrades to a blocking staged copy.  program_runtime holds the EXPOSED parts: copy_in = until the first
+// chunk is on the device, run = from there to the last kernel, copy_out = the rest of the wall time.
+snappy_status compress_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
+                                struct program_runtime* runtime)
+{
+    double t0 = now_seconds();
+    if (!input || !output || !runtime) return SNAPPY_INVALID_INPUT;
+    if (input->length && !input->buffer) return SNAPPY_INVALID_INPUT;
+    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+    if (!block_size_ok(block_size)) {
+        fprintf(stderr, "snappy_hip: block size %u is outside 1..65535 (16-bit hash table entries)\n", block_size);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (input->length > 0xffffffffull) {
+        fprintf(stderr, "snappy_hip: input of %lu bytes does not fit the format's uint32 length\n", input->length);
+        return SNAPPY_BUFFER_TOO_SMALL;
+    }
+    const uint64_t n = input->length;
+    const uint64_t nb = snappy_hip_num_blocks(n, block_size);
+    const ShardDevices devs = requested_devices();
+    if (devs.shards <= 0) {
+        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    const int gpus = dropin_plan::shard_count(devs.shards, nb);
+    const std::vector<dropin_plan::Range> part = dropin_plan::partition(nb, gpus, n, block_size);
+    std::vector<CompressShard> sh(part.begin(), part.end());
+    ShardCleanup<CompressShard> cleanup{sh, devs};
+    uint8_t hdr[10];
+    const uint32_t hdr_len = snappy_hip_write_header(hdr, (uint32_t)n, block_size);   // :523-525
+    const uint32_t stride = snappy_hip_slot_stride(block_size);
+    runtime->pre += now_seconds() - t0;
+    // One code path: a shard is a list of chunks; SNAPPY_HIP_PIPELINE_BLOCKS=0 (or a small shard) makes it one chunk, which
+    // is the strictly phased copy-in / run / copy-out of the reference (snappy_compress.c:547-704).
+    const uint64_t per = dropin_plan::shard_blocks(nb, gpus);
+    const uint64_t chunk_blocks =
+        dropin_plan::compress_chunk_blocks(per, dropin_plan::pipeline_chunk_blocks(per, block_size, getenv("SNAPPY_HIP_PIPELINE_BLOCKS")));
+
+    // alloc (dpu_alloc, snappy_compress.c:535)
+    snappy_status st = timed_phase(sh, devs, &runtime->d_alloc, "device allocation", [&](CompressShard& s, int) -> int {
+        const dropin_plan::CompressLayout l = dropin_plan::compress_layout(s.num_blocks, s.plain_len, block_size, stride, chunk_blocks);
+        s.chunks.assign(l.chunks.begin(), l.chunks.end());
+        s.scratch_bytes = snappy_hip_compress_scratch_bytes();          // for THIS device: its CU count sizes the scratch
+        HIP_TRY(s.alloc(&s.d_in, s.plain_len + 16));
+        HIP_TRY(s.alloc(&s.d_slots, s.num_blocks * (uint64_t)stride));
+        HIP_TRY(s.alloc(&s.d_bytes, s.num_blocks * sizeof(uint32_t)));
+        HIP_TRY(s.alloc(&s.d_offsets, l.offsets_pool));
+        HIP_TRY(s.alloc(&s.d_stream_len, dropin_plan::pad256(s.chunks.size() * sizeof(uint64_t))));
+        HIP_TRY(s.alloc(&s.d_stream, l.stream_pool));
+        for (size_t i = 0; i < std::min<size_t>(2, s.chunks.size()); ++i) HIP_TRY(s.alloc(&s.d_scratch[i], s.scratch_bytes));
+        for (CompressChunk& c : s.chunks)
+            for (hipEvent_t* e : {&c.ev_in, &c.ev_k1, &c.ev_run}) HIP_TRY(s.event(e));
+        return 0;
+    });
+    if (st) return st;
+
+    // load (dpu_load, :541): code object, copy engines, and this shard's streams with their hardware queues
+    st = timed_phase(sh, devs, &runtime->load, "code object load", [&](CompressShard& s, int g) -> int {
+        if (int r = warm_up_device()) return r;
+        return s.num_blocks ? pipeline_streams(devs.device_of(g), g, s.chunks.size(), &s.ps) : 0;
+    }, true);
+    if (st) return st;
+
+    // the output buffer: the caller's (finite max) or ours, grown when a chunk does not fit
+    const bool caller_owned = output->buffer && output->max != ~0UL;
+    uint64_t capacity = caller_owned ? output->max : 0;
+    if (!caller_owned) {
+        capacity = 32 + input->length + input->length / 6;      // the reference's own bound (snappy_compress.c:446-449)
+        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, capacity);
+        if (!nbuf) {
+            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)capacity);
+            return SNAPPY_BUFFER_TOO_SMALL;
+        }
+        output->buffer = nbuf;
+    }
+    if (capacity < hdr_len) {
+        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the stream header\n", (unsigned long)capacity);
+        return SNAPPY_BUFFER_TOO_SMALL;
+    }
+    memcpy(output->buffer, hdr, hdr_len);
+    uint64_t total = hdr_len;
+    bool too_small = false;
+    // place chunk c of shard s at `total` and start its copy-out
+    auto copy_out_chunk = [&](CompressShard& s, CompressChunk& c) -> int {
+        const uint64_t body = c.stream_len - c.local_hdr;
+        c.out_off = total;
+        if (total + body > capacity) {
+            if (caller_owned) {
+                too_small = true;
+                total += body;
+                return 0;
+            }
+            // copies into the old buffer must land before it moves: every shard's copy-out stream, each on its own device
+            // (this runs either on shard 0's thread inside the pipeline or on the caller's thread after the join)
+            int here = 0;
+            HIP_TRY(hipGetDevice(&here));
+            for (size_t g2 = 0; g2 < sh.size(); ++g2) {
+                if (!sh[g2].num_blocks || !sh[g2].ps.out) continue;
+                HIP_TRY(hipSetDevice(devs.device_of((int)g2)));
+                HIP_TRY(hipStreamSynchronize(sh[g2].ps.out));
+            }
+            HIP_TRY(hipSetDevice(here));
+            capacity = std::max(total + body, capacity + capacity / 2);
+            uint8_t* nbuf = (uint8_t*)realloc(output->buffer, capacity);
+            if (!nbuf) return fail(SNAPPY_HIP_ERR_RUNTIME, "cannot grow the output buffer");
+            output->buffer = nbuf;
+        }
+        if (!too_small)
+            HIP_TRY(hipMemcpyAsync(output->buffer + c.out_off, s.d_stream + c.stream_at + c.local_hdr, body, hipMemcpyDeviceToHost,
+                                   s.ps.out));
+        total += body;
+        return 0;
+    };
+
+    // the pipeline (:547-704).  Shard 0 knows where its output goes and copies out as it runs; later shards learn their
+    // place once every earlier shard has reported its lengths, and copy out after the join.
+    t0 = now_seconds();
+    int rc = on_shards(sh, devs, [&](CompressShard& s, int g) -> int {
+        const size_t n = s.chunks.size();
+        auto copy_in = [&](size_t k) -> int {
+            CompressChunk& c = s.chunks[k];
+            HIP_TRY(hipMemcpyAsync(s.d_in + c.plain_off, input->buffer + s.plain_off + c.plain_off, c.plain_len, hipMemcpyHostToDevice,
+                                   s.ps.in));
+            HIP_TRY(hipEventRecord(c.ev_in, s.ps.in));
+            return 0;
+        };
+        auto finish = [&](size_t k) -> int {
+            CompressChunk& c = s.chunks[k];
+            HIP_TRY(hipEventSynchronize(c.ev_run));
+            c.stream_len = s.ps.h_len[k];
+            return g == 0 ? copy_out_chunk(s, c) : 0;
+        };
+        HIP_TRY(hipEventRecord(s.ps.start, s.ps.in));
+        if (int r = copy_in(0)) return r;
+        for (size_t k = 0; k < n; ++k) {
+            CompressChunk& c = s.chunks[k];
+            uint8_t* slots = s.d_slots + c.first_block * (uint64_t)stride;
+            // Two launches in flight, on alternating streams with a hash-table scratch each: a launch of one block per
+            // wavefront ends in a tail of half-empty CUs, which the next chunk's wavefronts fill.
+            hipStream_t run = (k & 1) ? s.ps.run2 : s.ps.run;
+            HIP_TRY(hipStreamWaitEvent(run, c.ev_in, 0));
+            int r = snappy_hip_compress_blocks(s.d_in + c.plain_off, c.plain_len, block_size, slots, stride, s.d_bytes + c.first_block,
+                                               s.d_scratch[k & 1], s.scratch_bytes, run);
+            if (r) return r;
+            // scan + gather on a stream of their own: small kernels that crawl beside the next chunk's K1 must not
+            // hold back the K1 launch after that
+            HIP_TRY(hipEventRecord(c.ev_k1, run));
+            HIP_TRY(hipStreamWaitEvent(s.ps.post, c.ev_k1, 0));
+            r = snappy_hip_compact(slots, stride, s.d_bytes + c.first_block, c.plain_len, block_size, s.d_stream + c.stream_at,
+                                   (uint64_t*)(s.d_offsets + c.offsets_at), s.d_stream_len + k, s.ps.post);
+            if (r) return r;
+            HIP_TRY(hipMemcpyAsync(&s.ps.h_len[k], s.d_stream_len + k, sizeof(uint64_t), hipMemcpyDeviceToHost, s.ps.post));
+            HIP_TRY(hipEventRecord(c.ev_run, s.ps.post));
+            if (k + 1 < n)
+                if (int r2 = copy_in(k + 1)) return r2;
+            if (k >= 1)
+                if (int r2 = finish(k - 1)) return r2;
+        }
+        if (int r = finish(n - 1)) return r;
+        HIP_TRY(hipStreamSynchronize(s.ps.out));
+        HIP_TRY(hipEventElapsedTime(&s.exposed_in_ms, s.ps.start, s.chunks[0].ev_in));
+        HIP_TRY(hipEventElapsedTime(&s.kernel_ms, s.chunks[0].ev_in, s.chunks[n - 1].ev_run));
+        if (env_int("SNAPPY_HIP_PIPELINE_TRACE", 0))
+            for (size_t k = 0; k < n; ++k) {
+                float a = 0.f, b = 0.f, c = 0.f;
+                HIP_TRY(hipEventElapsedTime(&a, s.ps.start, s.chunks[k].ev_in));
+                HIP_TRY(hipEventElapsedTime(&b, s.ps.start, s.chunks[k].ev_k1));
+                HIP_TRY(hipEventElapsedTime(&c, s.ps.start, s.chunks[k].ev_run));
+                fprintf(stderr, "chunk %zu: copied in at %.2f ms, compressed at %.2f ms, framed at %.2f ms\n", k, a, b, c);
+            }
+        if (n >= 2) {                                   // the second-to-last launch runs on the other stream and may end later
+            float other = 0.f;
+            HIP_TRY(hipEventElapsedTime(&other, s.chunks[0].ev_in, s.chunks[n - 2].ev_run));
+            s.kernel_ms = std::max(s.kernel_ms, other);
+        }
+        return 0;
+    });
+    if (rc) return report("compress pipeline");
+    if (sh.size() > 1) {
+        for (size_t g = 1; g < sh.size() && !rc; ++g) {
+            CompressShard& s = sh[g];
+            if (!s.num_blocks) continue;
+            if ((rc = (int)hipSetDevice(devs.device_of((int)g)))) break;
+            for (auto& c : s.chunks)
+                if ((rc = copy_out_chunk(s, c))) break;
+        }
+        if (!rc)
+            rc = on_shards(sh, devs, [](CompressShard& s, int g) -> int {
+                if (g) HIP_TRY(hipStreamSynchronize(s.ps.out));
+                return 0;
+            });
+        if (rc) return report("device-to-host copy");
+    }
+    st = finish_shards(sh, devs, runtime, now_seconds() - t0, [](const CompressShard& s) { return s.plain_len; });
+    if (st) return st;
+    if (too_small) {
+        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the %lu-byte stream\n", (unsigned long)output->max,
+                (unsigned long)total);
+        return SNAPPY_BUFFER_TOO_SMALL;
+    }
+    if (!caller_owned) {
+        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, total ? total : 1);
+        if (nbuf) output->buffer = nbuf;
+    }
+    output->length = total;
+    output->curr = output->buffer + total;
+    return SNAPPY_OK;
+}
+
+// Decompress counterpart: sizes are known from the host pre-scan, so the whole pipeline is enqueued without a host
+// round trip; chunk k's plaintext goes straight into its range of output->buffer (snappy_decompress.c:463).
+snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    double t0 = now_seconds();
+    if (!input || !output || !runtime) return SNAPPY_INVALID_INPUT;
+    if (!input->buffer || !input->curr || input->curr < input->buffer) return SNAPPY_INVALID_INPUT;
+    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+
+    // block-size varint (snappy_decompress.c:298-303)
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length;
+    uint64_t at = (uint64_t)(input->curr - input->buffer);
+    uint32_t bs = 0;
+    const uint32_t used = (at <= in_total) ? get_varint32(buf + at, in_total - at, &bs) : 0;
+    if (!used) {
+        fprintf(stderr, "Failed to read decompressed block size\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    at += used;
+    input->curr += used;
+    const uint64_t total = output->length;
+    if (total == 0) {
+        runtime->pre += now_seconds() - t0;
+        return (at == in_total) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
+    }
+    if (!block_size_ok(bs)) {
+        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (!output->buffer) {
+        fprintf(stderr, "snappy_hip: output->buffer is NULL (setup_decompression allocates it, snappy_decompress.c:207-209)\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    const uint64_t nb = snappy_hip_num_blocks(total, bs);
+    // the header is untrusted: every block needs at least its u32 size prefix, so a stream of in_total - at bytes cannot
+    // hold more than (in_total - at) / 4 blocks -- checked before anything is sized by nb
+    if (nb > (in_total - at) / 4) {
+        fprintf(stderr, "snappy_hip: header promises %lu blocks, the stream has room for %lu\n", (unsigned long)nb,
+                (unsigned long)((in_total - at) / 4));
+        return SNAPPY_INVALID_INPUT;
+    }
+    const ShardDevices devs = requested_devices();
+    if (devs.shards <= 0) {
+        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    const int gpus = dropin_plan::shard_count(devs.shards, nb);
+    const uint64_t per = dropin_plan::shard_blocks(nb, gpus);
+    const dropin_plan::DecompressChunking plan = dropin_plan::decompress_chunking(
+        per, dropin_plan::pipeline_chunk_blocks(per, bs, getenv("SNAPPY_HIP_PIPELINE_BLOCKS")), gpus);
+    const std::vector<dropin_plan::Range> part = dropin_plan::partition(nb, gpus, total, bs);
+    std::vector<DecompressShard> sh(part.begin(), part.end());
+    ShardCleanup<DecompressShard> cleanup{sh, devs};
+    std::vector<uint64_t> off;          // every block's stream offset, unless the one shard walks the chain in its pipeline
+    if (plan.walk_in_pipeline) {
+        sh[0].in_off = at;
+        sh[0].in_len = in_total - at;
+    } else {
+        // host pre-scan of the size chain (:306-341): every offset is needed before the blocks are split over devices.  In
+        // parallel shares where the stream is long enough (csrc/host_chain.hpp; the serial chase costs ~7 ms per GiB, all
+        // of `pre`); SNAPPY_HIP_HOST_WALK_THREADS=1 is the serial walk alone, which also names a damaged stream's fault.
+        const unsigned walk_threads = (unsigned)std::max(1, env_int("SNAPPY_HIP_HOST_WALK_THREADS",
+                                                                   (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
+        if (!host_chain::parallel_walk(buf, in_total, at, nb, bs, walk_threads, off)) {
+            off.assign(nb + 1, 0);
+            const dropin_plan::Walk w = dropin_plan::walk_chain(buf, in_total, 0, off.data(), {0, at}, nb);
+            const std::string err = dropin_plan::whole_walk_error(w, nb, in_total);
+            if (!err.empty()) {
+                fprintf(stderr, "snappy_hip: %s\n", err.c_str());
+                return SNAPPY_INVALID_INPUT;
+            }
+        }
+        for (DecompressShard& s : sh) {
+            s.in_off = off[s.first_block];
+            s.in_len = off[s.first_block + s.num_blocks] - s.in_off;
+        }
+    }
+    runtime->pre += now_seconds() - t0;
+    snappy_status st = timed_phase(sh, devs, &runtime->d_alloc, "device allocation", [&](DecompressShard& s, int) -> int {
+        const std::vector<dropin_plan::Range> chunks = dropin_plan::split_blocks(s.num_blocks, s.plain_len, bs, plan.chunk_blocks);
+        s.chunks.assign(chunks.begin(), chunks.end());
+        for (DecompressChunk& c : s.chunks)
+            for (hipEvent_t* e : {&c.ev_in, &c.ev_run}) HIP_TRY(s.event(e));
+        HIP_TRY(s.alloc(&s.d_stream, s.in_len + 16));
+        HIP_TRY(s.alloc(&s.d_boff, s.num_blocks * sizeof(uint64_t)));
+        HIP_TRY(s.alloc(&s.d_out, s.plain_len + 16));
+        HIP_TRY(s.alloc(&s.d_status, s.num_blocks * sizeof(uint32_t)));
+        return 0;
+    });
+    if (st) return st;
+
+    st = timed_phase(sh, devs, &runtime->load, "code object load", [&](DecompressShard& s, int g) -> int {
+        if (int r = warm_up_device()) return r;
+        if (!s.num_blocks) return 0;
+        if (int r = pipeline_streams(devs.device_of(g), g, s.num_blocks + 1, &s.ps)) return r;   // page-locked home of the block offsets
+        s.walk = {0, s.in_off};
+        if (!off.empty()) {                                                 // chain already walked, in `pre`
+            for (uint64_t i = 0; i <= s.num_blocks; ++i) s.ps.h_len[i] = off[s.first_block + i] - s.in_off;
+            s.walk = {s.num_blocks, s.in_off + s.in_len};
+        }
+        return 0;
+    }, true);
+    if (st) return st;
+
+    t0 = now_seconds();
+    int rc = on_shards(sh, devs, [&](DecompressShard& s, int) -> int {
+        const size_t n = s.chunks.size();
+        const uint64_t* rel = s.ps.h_len;
+        auto copy_out = [&](size_t k) -> int {
+            DecompressChunk& c = s.chunks[k];
+            HIP_TRY(hipStreamWaitEvent(s.ps.out, c.ev_run, 0));
+            HIP_TRY(hipMemcpyAsync(output->buffer + s.plain_off + c.plain_off, s.d_out + c.plain_off, c.plain_len, hipMemcpyDeviceToHost,
+                                   s.ps.out));
+            return 0;
+        };
+        HIP_TRY(hipEventRecord(s.ps.start, s.ps.in));
+        size_t issued = 0;
+        for (size_t k = 0; k < n; ++k) {
+            DecompressChunk& c = s.chunks[k];
+            // the host walks this chunk's part of the size chain while the previous chunk is still being copied in
+            s.walk = dropin_plan::walk_chain(buf, in_total, s.in_off, s.ps.h_len, s.walk, c.first_block + c.num_blocks);
+            if (s.walk.stop != dropin_plan::kDone) {
+                s.bad_chain = true;
+                break;
+            }
+            const uint64_t in_off = rel[c.first_block], in_len = rel[c.first_block + c.num_blocks] - in_off;   // in the shard's slice
+            HIP_TRY(hipMemcpyAsync(s.d_boff + c.first_block, rel + c.first_block, c.num_blocks * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                   s.ps.in));
+            HIP_TRY(hipMemcpyAsync(s.d_stream + in_off, buf + s.in_off + in_off, in_len, hipMemcpyHostToDevice, s.ps.in));
+            HIP_TRY(hipEventRecord(c.ev_in, s.ps.in));
+            HIP_TRY(hipStreamWaitEvent(s.ps.run, c.ev_in, 0));
+            // block i of the chunk is read at d_stream + d_boff[first + i] (offsets stay relative to the shard's slice)
+            int r = snappy_hip_decompress_blocks(s.d_stream, s.in_len, s.d_boff + c.first_block, c.plain_len, bs, s.d_out + c.plain_off,
+                                                 s.d_status + c.first_block, s.ps.run);
+            if (r) return r;
+            HIP_TRY(hipEventRecord(c.ev_run, s.ps.run));
+            ++issued;
+            if (k >= 1)
+                if (int r2 = copy_out(k - 1)) return r2;
+        }
+        if (!s.bad_chain && s.walk.at != s.in_off + s.in_len) s.bad_chain = true;    // the chain must end where the slice ends
+        if (issued && !s.bad_chain)
+            if (int r = copy_out(issued - 1)) return r;
+        HIP_TRY(hipStreamSynchronize(s.ps.in));
+        HIP_TRY(hipStreamSynchronize(s.ps.run));
+        HIP_TRY(hipStreamSynchronize(s.ps.out));
+        if (s.bad_chain || !issued) return 0;
+        std::vector<uint32_t> status(s.num_blocks);
+        HIP_TRY(hipMemcpy(status.data(), s.d_status, s.num_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < s.num_blocks; ++i)
+            if (status[i] != SNAPPY_HIP_BLOCK_OK) s.bad = true;
+        HIP_TRY(hipEventElapsedTime(&s.exposed_in_ms, s.ps.start, s.chunks[0].ev_in));
+        HIP_TRY(hipEventElapsedTime(&s.kernel_ms, s.chunks[0].ev_in, s.chunks[n - 1].ev_run));
+        return 0;
+    });
+    const double wall = now_seconds() - t0;
+    if (rc) return report("decompress pipeline");
+    if ((st = finish_shards(sh, devs, runtime, wall, [](const DecompressShard& s) { return s.in_len; }))) return st;
+    for (auto& s : sh) {
+        if (s.bad_chain) {
+            fprintf(stderr, "snappy_hip: size chain leaves the stream (block %lu of %lu)\n",
+                    (unsigned long)(s.first_block + s.walk.block), (unsigned long)(s.first_block + s.num_blocks));
+            return SNAPPY_INVALID_INPUT;
+        }
+        if (s.bad) {
+            fprintf(stderr, "snappy_hip: malformed block in the stream\n");
+            return SNAPPY_INVALID_INPUT;
+        }
+    }
+    output->curr = output->buffer + total;
+    return SNAPPY_OK;
+}
+
+// The exported pair: one call at a time per process (the cached pipeline streams and their page-locked scratch are per
+// process; the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618), the caller's
+// current HIP device restored on every return path, and no C++ exception crosses the C boundary.
+template <class Body>
+snappy_status entry_guard(Body body)
+{
+    try {
+        std::lock_guard<std::mutex> one_at_a_time(*pipeline_mutex());
+        CallerDevice keep;
+        return body();
+    } catch (const std::bad_alloc&) {
+        fprintf(stderr, "snappy_hip: out of host memory\n");
+        return SNAPPY_BUFFER_TOO_SMALL;
+    } catch (const std::exception& e) {
+        fprintf(stderr, "snappy_hip: %s\n", e.what());
+        return SNAPPY_INVALID_INPUT;
+    } catch (...) {
+        return SNAPPY_INVALID_INPUT;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+snappy_status snappy_compress_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
+                                  struct program_runtime* runtime)
+{
+    return entry_guard([&] { return compress_gpu_body(input, output, block_size, runtime); });
+}
+
+snappy_status snappy_decompress_gpu(struct host_buffer_context* input, struct host_buffer_context* output,
+                                    struct program_runtime* runtime)
+{
+    return entry_guard([&] { return decompress_gpu_body(input, output, runtime); });
+}
+
+}  // extern "C"

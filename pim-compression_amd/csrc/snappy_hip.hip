@@ -23,7 +23,7 @@
 #include "../../include/snappy_hip.h"
 #include "shard_devices.hpp"
 #include "launch_shape.hpp"
-#include "host_chain.hpp"
+#include "dropin_plan.hpp"
 #include "snappy_kernels.hpp"
 
 namespace {
@@ -73,11 +73,6 @@ uint32_t get_varint32(const uint8_t* src, uint64_t avail, uint32_t* out)   // sn
         }
     }
     return 0;
-}
-
-uint32_t le32_host(const uint8_t* p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
 bool block_size_ok(uint32_t bs) { return bs >= SNAPPY_HIP_MIN_BLOCK_SIZE && bs <= SNAPPY_HIP_MAX_BLOCK_SIZE; }
@@ -848,890 +843,6 @@ int snappy_hip_decompress_blocks_batch(const struct snappy_hip_decompress_item* 
     return SNAPPY_HIP_OK;
 }
 
-}  // extern "C"
-
-// ===========================================================================
-// drop-in pair (reference L2 signatures)
-// ===========================================================================
-
-namespace {   // (C++ linkage: an unnamed namespace inside extern "C" would still export unmangled names)
-
-// One pipeline stage unit of the overlapped drop-in pair: a contiguous run of blocks of a shard whose copy-in, kernels
-// and copy-out overlap those of its neighbours.
-struct CompressChunk {
-    uint64_t first_block = 0, num_blocks = 0;   // relative to the shard
-    uint64_t in_off = 0, in_len = 0;            // relative to the shard's input slice
-    uint8_t* d_stream = nullptr;                // this chunk's own framed stream (local header + blocks)
-    uint64_t *d_offsets = nullptr, *d_stream_len = nullptr;
-    uint32_t local_hdr = 0;
-    uint64_t stream_len = 0, out_off = 0;
-    hipEvent_t ev_in = nullptr, ev_k1 = nullptr, ev_run = nullptr;
-};
-
-struct DecompressChunk {
-    uint64_t first_block = 0, num_blocks = 0;   // relative to the shard
-    uint64_t in_off = 0, in_len = 0;            // relative to the shard's slice of the stream
-    uint64_t out_off = 0, out_len = 0;          // relative to the shard's slice of the output
-    hipEvent_t ev_in = nullptr, ev_run = nullptr;
-};
-
-// The compress pipeline keeps six streams busy at once (copy-in, two K1 launches, the LDS-table helper, framing,
-// copy-out).  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams on
-// one queue run in enqueue order: measured here, the copy-in of chunk k+1 then waits for the K1 launch of chunk k and the
-// pipeline degenerates to the phased form (38 instead of 52 GB/s on a 3 GiB input).  The library does NOT touch the
-// process environment: a host program that wants the overlap exports GPU_MAX_HW_QUEUES=8 before its first HIP call (the
-// CLI and the Python binding do); without it only the overlap is lost, never bytes.
-
-// Streams of one shard's pipeline.  Creating a stream costs milliseconds (a hardware queue each), so the sets are made
-// once per process and shard index and kept: a long-lived caller pays for them in its first call only.
-struct PipelineStreams {
-    hipStream_t in = nullptr, run = nullptr, run2 = nullptr, post = nullptr, out = nullptr;
-    hipEvent_t start = nullptr;
-    uint64_t* h_len = nullptr;          // page-locked scratch: stream length per chunk / block offsets
-    size_t h_len_count = 0;
-};
-
-// The cached streams and their page-locked scratch are per process, so overlapped calls from several host threads take
-// turns (the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618).
-std::mutex* pipeline_mutex()
-{
-    static std::mutex* m = new std::mutex;
-    return m;
-}
-
-// Cached per (device, shard): streams, events and the DMA queues behind them belong to the device they were created on, and
-// the shard-to-device mapping follows the caller's current device (ShardDevices), so shard g of one call and shard g of the
-// next may run on different devices; two shards on ONE device (SNAPPY_HIP_OVERSUBSCRIBE) run in different host threads at
-// the same time and must not share a set either.
-int pipeline_streams(int device, int shard, size_t chunks, PipelineStreams** out)
-{
-    static std::map<int, PipelineStreams*> cache;
-    static std::mutex cache_mutex;
-    if (shard < 0 || shard >= 64 || device < 0 || device >= 64) return fail(SNAPPY_HIP_ERR_ARG, "shard / device index out of range");
-    PipelineStreams* pp = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(cache_mutex);
-        PipelineStreams*& slot = cache[pipeline_stream_key(device, shard)];
-        if (!slot) slot = new PipelineStreams;               // never destroyed (threads may outlive statics)
-        pp = slot;
-    }
-    PipelineStreams& p = *pp;                            // one (device, shard) is only ever touched by the host thread driving that shard
-    if (!p.in) {
-        HIP_TRY(hipStreamCreateWithFlags(&p.in, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&p.run, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&p.run2, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&p.post, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&p.out, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&p.start));
-        // a stream gets its hardware queue at first use: use each one now, in the load phase, not under the first chunk
-        for (hipStream_t st : {p.in, p.run, p.run2, p.post, p.out}) {
-            WorkCounter c;
-            if (int rc = next_work_counter(&c, st)) return rc;
-            if (int rc = work_counter_launched(c, st)) return rc;
-        }
-        // ... and the first asynchronous copy in either direction on a stream starts a DMA queue of its own (~8 ms)
-        const size_t n = 256u << 10;
-        void *h = nullptr, *d = nullptr;
-        HIP_TRY(hipHostMalloc(&h, n, hipHostMallocPortable));
-        HIP_TRY(hipMalloc(&d, n));
-        memset(h, 0, n);
-        HIP_TRY(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, p.in));
-        HIP_TRY(hipStreamSynchronize(p.in));
-        for (hipStream_t st : {p.out, p.post, p.run, p.run2}) HIP_TRY(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(d);
-        (void)hipHostFree(h);
-    }
-    if (chunks > p.h_len_count) {
-        if (p.h_len) (void)hipHostFree(p.h_len);
-        p.h_len = nullptr;
-        p.h_len_count = 0;
-        const size_t want = std::max<size_t>(chunks, 64);
-        HIP_TRY(hipHostMalloc((void**)&p.h_len, want * sizeof(uint64_t), hipHostMallocPortable));
-        p.h_len_count = want;
-    }
-    *out = &p;
-    return 0;
-}
-
-// SNAPPY_HIP_PIPELINE_BLOCKS: blocks per pipeline chunk of the drop-in pair (0 = strictly phased copy-in / run /
-// copy-out, the reference's own order).  Default: 4096 blocks -- a K1 launch of one block per resident wavefront, and
-// 128 MiB per copy -- shrinking to a quarter of the shard (not below 2048) so that a 256 MiB file still overlaps.
-uint64_t pipeline_chunk_blocks(uint64_t shard_blocks, uint32_t block_size)
-{
-    const char* v = getenv("SNAPPY_HIP_PIPELINE_BLOCKS");
-    if (v && *v) return atoi(v) > 0 ? (uint64_t)atoi(v) : 0;
-    // the chunk is sized in BYTES (128 MiB, at least 64 MiB): with small blocks a chunk of 4096 blocks would be a 16 MiB
-    // copy and a 0.2 ms launch, and the pipeline would be bound by launches
-    const uint64_t scale = std::max<uint64_t>(1, 32768 / std::max<uint32_t>(block_size, 1));
-    const uint64_t quarter = ((shard_blocks + 3) / 4 + 15) & ~15ull;
-    return std::min<uint64_t>(4096 * scale, std::max<uint64_t>(2048 * scale, quarter));
-}
-
-// split `nb` blocks into equal chunks of at most `chunk` blocks, each a multiple of 16 blocks (keeps every chunk's
-// input slice 16-byte aligned whatever the block size)
-struct BlockRange {
-    uint64_t first, second;
-};
-void split_blocks(uint64_t nb, uint64_t chunk, std::vector<BlockRange>& v)
-{
-    v.clear();
-    if (!nb) return;
-    const uint64_t parts = (nb + chunk - 1) / chunk;
-    uint64_t per = (nb + parts - 1) / parts;
-    per = (per + 15) & ~15ull;
-    for (uint64_t b = 0; b < nb; b += per) v.push_back(BlockRange{b, std::min(per, nb - b)});
-}
-
-struct CompressShard {
-    uint64_t first_block = 0, num_blocks = 0;
-    uint64_t in_off = 0, in_len = 0;
-    uint8_t *d_in = nullptr, *d_slots = nullptr, *d_stream = nullptr;
-    uint32_t* d_bytes = nullptr;
-    uint64_t *d_offsets = nullptr, *d_stream_len = nullptr;
-    void *d_scratch = nullptr, *d_scratch2 = nullptr;
-    float kernel_ms = 0.f;
-    std::vector<CompressChunk> chunks;      // one chunk = the phased form
-    PipelineStreams ps;
-    float exposed_in_ms = 0.f;
-
-    bool owns_anything() const { return d_in || d_slots || d_bytes || d_offsets || d_stream_len || d_scratch || d_scratch2 || d_stream; }
-    // device memory and per-chunk events (the cached streams stay); safe to call twice
-    void release()
-    {
-        for (auto& c : chunks) {
-            if (c.ev_in) (void)hipEventDestroy(c.ev_in);
-            if (c.ev_k1) (void)hipEventDestroy(c.ev_k1);
-            if (c.ev_run) (void)hipEventDestroy(c.ev_run);
-            c.ev_in = c.ev_k1 = c.ev_run = nullptr;
-        }
-        void** owned[] = {(void**)&d_in, (void**)&d_slots, (void**)&d_bytes, (void**)&d_offsets, (void**)&d_stream_len,
-                          &d_scratch, &d_scratch2, (void**)&d_stream};
-        for (void** q : owned) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-    }
-};
-
-struct DecompressShard {
-    uint64_t first_block = 0, num_blocks = 0;
-    uint64_t in_off = 0, in_len = 0;      // slice of the compressed stream (relative to input->buffer)
-    uint64_t out_off = 0, out_len = 0;
-    uint8_t *d_stream = nullptr, *d_out = nullptr;
-    uint64_t* d_boff = nullptr;
-    uint32_t* d_status = nullptr;
-    std::vector<uint64_t> rel_off;
-    float kernel_ms = 0.f;
-    bool bad = false;
-    std::vector<DecompressChunk> chunks;    // one chunk = the phased form
-    PipelineStreams ps;
-    float exposed_in_ms = 0.f;
-    // size chain of the shard (snappy_decompress.c:317-340), walked on demand: blocks [0, walked) have their offsets
-    // (relative to in_off) in ps.h_len[], [walked] holds the end of the last one; walk_at = stream position of block `walked`
-    uint64_t walked = 0, walk_at = 0;
-    bool bad_chain = false;
-
-    bool owns_anything() const { return d_stream || d_boff || d_out || d_status; }
-    void release()
-    {
-        for (auto& c : chunks) {
-            if (c.ev_in) (void)hipEventDestroy(c.ev_in);
-            if (c.ev_run) (void)hipEventDestroy(c.ev_run);
-            c.ev_in = c.ev_run = nullptr;
-        }
-        void** owned[] = {(void**)&d_stream, (void**)&d_boff, (void**)&d_out, (void**)&d_status};
-        for (void** q : owned) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
-    }
-};
-
-// Error returns leave through this: drain every device a shard used, then give its memory back (the normal path has
-// released everything in its timed "free" phase by then, and release() is idempotent).
-struct CompressCleanup {
-    std::vector<CompressShard>& shards;
-    const ShardDevices& devs;
-    ~CompressCleanup()
-    {
-        bool any = false;
-        for (auto& s : shards) any = any || s.owns_anything();
-        if (!any) return;
-        for (size_t g = 0; g < shards.size(); ++g) {
-            if (hipSetDevice(devs.device_of((int)g)) == hipSuccess) (void)hipDeviceSynchronize();
-            shards[g].release();
-        }
-    }
-};
-struct DecompressCleanup {
-    std::vector<DecompressShard>& shards;
-    const ShardDevices& devs;
-    ~DecompressCleanup()
-    {
-        bool any = false;
-        for (auto& s : shards) any = any || s.owns_anything();
-        if (!any) return;
-        for (size_t g = 0; g < shards.size(); ++g) {
-            if (hipSetDevice(devs.device_of((int)g)) == hipSuccess) (void)hipDeviceSynchronize();
-            shards[g].release();
-        }
-    }
-};
-
-// extend the walk so that blocks [0, upto) are known; false = the chain leaves the stream
-bool walk_chain(DecompressShard& s, uint64_t upto, const uint8_t* buf, uint64_t in_total)
-{
-    uint64_t* rel = s.ps.h_len;
-    while (s.walked < upto) {
-        if (s.walk_at + 4 > in_total) return false;
-        rel[s.walked] = s.walk_at - s.in_off;
-        s.walk_at += 4 + (uint64_t)le32_host(buf + s.walk_at);
-        if (s.walk_at > in_total) return false;
-        ++s.walked;
-    }
-    rel[s.walked] = s.walk_at - s.in_off;
-    return true;
-}
-
-// "load" phase (dpu_load, snappy_compress.c:541): make the device ready so that the copy and run phases measure
-// copies and kernels -- code object on the device, copy engines and the co-run helper stream initialised.
-int warm_up_device()
-{
-    hipFuncAttributes fa;
-    // (the default K1 launch for blocks of more than 8 KiB: the cached global-table kernel and the LDS-table kernel, stream form)
-    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::compress_blocks_global_table_kernel<64, 3, 1, 512>)));
-    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::compress_blocks_lds_table_kernel<64, 3>)));
-    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::gather_slots_kernel)));
-    HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(snappy_hip::decompress_blocks_kernel)));
-    CoRunResources* cr = nullptr;
-    if (int rc = corun_resources(&cr)) return rc;
-    WorkCounter c;
-    if (int rc = next_work_counter(&c, nullptr)) return rc;      // also touches the module's globals
-    uint32_t probe = 0;
-    HIP_TRY(hipMemcpy(&probe, c.ptr, sizeof(probe), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(c.ptr, &probe, sizeof(probe), hipMemcpyHostToDevice));
-    if (int rc = work_counter_launched(c, nullptr)) return rc;
-    // the first copy of more than a few KiB in either direction starts the DMA engines (~8 ms, once per process)
-    static std::mutex engines_mutex;
-    static bool engines_started[64] = {};                        // per process and device, not per (short-lived) shard thread
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> engines_lock(engines_mutex);
-    if (dev >= 0 && dev < 64 && !engines_started[dev]) {
-        const size_t n = 1u << 20;
-        void *h = nullptr, *d = nullptr;
-        HIP_TRY(hipHostMalloc(&h, n, hipHostMallocPortable));
-        HIP_TRY(hipMalloc(&d, n));
-        memset(h, 0, n);
-        HIP_TRY(hipMemcpy(d, h, n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h, d, n, hipMemcpyDeviceToHost));
-        (void)hipFree(d);
-        (void)hipHostFree(h);
-        engines_started[dev] = true;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return 0;
-}
-
-// copy_in / run = the slowest shard's exposed copy-in and kernel time (the shards run side by side, so the phase lasts as
-// long as its slowest member); copy_out = what is left of the section's wall time, so the three still add up to it.
-extern "C++" template <class Shard>
-void shard_phase_times(const std::vector<Shard>& sh, struct program_runtime* runtime, double wall)
-{
-    float in_ms = 0.f, run_ms = 0.f;
-    for (const Shard& s : sh) {
-        in_ms = std::max(in_ms, s.exposed_in_ms);
-        run_ms = std::max(run_ms, s.kernel_ms);
-    }
-    runtime->copy_in = in_ms / 1000.0;
-    runtime->run = run_ms / 1000.0;
-    runtime->copy_out = std::max(0.0, wall - runtime->copy_in - runtime->run);
-}
-
-snappy_status report(const char* where, int rc)
-{
-    fprintf(stderr, "snappy_hip: %s failed: %s\n", where, g_last_error.c_str());
-    (void)rc;
-    return SNAPPY_INVALID_INPUT;   // the reference maps a failed launch to this (snappy_compress.c:618-623)
-}
-
-
-// ---------------------------------------------------------------------------
-// The drop-in pair's device side (phases of snappy_compress.c:528-709 / snappy_decompress.c:306-493), overlapped per
-// SURVEY section 8f row 3.  Each shard is cut into chunks of SNAPPY_HIP_PIPELINE_BLOCKS blocks; chunk k+1 is copied in
-// while chunk k is compressed / decoded and chunk k-1 is framed and copied out, on separate streams.  With one chunk per
-// shard this IS the reference's phased order.  The bytes do not depend on the chunking: chunks are whole blocks, blocks
-// are independent (snappy_compress.c:473, :286), and the host concatenates chunk streams exactly as it concatenates
-// per-device streams.  The enqueue order (kernels of k, then copy-in of k+1, then copy-out of k-1) keeps
-// the overlap when the caller's buffers are pageable and hipMemcpyAsync degrades to a blocking staged copy.
-// program_runtime then holds the EXPOSED parts: copy_in = until the first chunk is on the device, run = from there to
-// the last kernel, copy_out = what is left of the wall time.
-// ---------------------------------------------------------------------------
-snappy_status compress_pipelined(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
-                                 struct program_runtime* runtime, std::vector<CompressShard>& sh, int gpus, const ShardDevices& devs,
-                                 const uint8_t* hdr,
-                                 uint32_t hdr_len, uint32_t stride, uint64_t chunk_blocks)
-{
-    const uint64_t scratch_bytes = snappy_hip_compress_scratch_bytes();
-    auto pad = [](uint64_t v) { return (v + 255) & ~255ull; };
-
-    // alloc (dpu_alloc, snappy_compress.c:535)
-    double t0 = now_seconds();
-    int rc = for_each_device(gpus, [&](int g) -> int {
-        CompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        if (!s.num_blocks) return 0;
-        uint64_t stream_pool = 0, offsets_pool = 0;
-        std::vector<BlockRange> ranges;
-        split_blocks(s.num_blocks, chunk_blocks, ranges);
-        for (auto& fb : ranges) {
-            CompressChunk c;
-            c.first_block = fb.first;
-            c.num_blocks = fb.second;
-            c.in_off = c.first_block * block_size;
-            c.in_len = std::min<uint64_t>(s.in_len - c.in_off, c.num_blocks * (uint64_t)block_size);
-            uint8_t tmp[10];
-            c.local_hdr = snappy_hip_write_header(tmp, (uint32_t)c.in_len, block_size);
-            stream_pool += pad(snappy_hip_stream_bound(c.in_len, block_size));
-            offsets_pool += pad((c.num_blocks + 1) * sizeof(uint64_t));
-            s.chunks.push_back(c);
-        }
-        HIP_TRY(hipMalloc((void**)&s.d_in, s.in_len + 16));
-        HIP_TRY(hipMalloc((void**)&s.d_slots, s.num_blocks * (uint64_t)stride));
-        HIP_TRY(hipMalloc((void**)&s.d_bytes, s.num_blocks * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&s.d_offsets, offsets_pool));
-        HIP_TRY(hipMalloc((void**)&s.d_stream_len, pad(s.chunks.size() * sizeof(uint64_t))));
-        HIP_TRY(hipMalloc((void**)&s.d_stream, stream_pool));
-        HIP_TRY(hipMalloc(&s.d_scratch, scratch_bytes));
-        if (s.chunks.size() > 1) HIP_TRY(hipMalloc(&s.d_scratch2, scratch_bytes));
-        uint64_t stream_at = 0, offsets_at = 0;
-        for (size_t k = 0; k < s.chunks.size(); ++k) {
-            CompressChunk& c = s.chunks[k];
-            c.d_stream = s.d_stream + stream_at;
-            c.d_offsets = (uint64_t*)((uint8_t*)s.d_offsets + offsets_at);
-            c.d_stream_len = s.d_stream_len + k;
-            stream_at += pad(snappy_hip_stream_bound(c.in_len, block_size));
-            offsets_at += pad((c.num_blocks + 1) * sizeof(uint64_t));
-            HIP_TRY(hipEventCreate(&c.ev_in));
-            HIP_TRY(hipEventCreate(&c.ev_k1));
-            HIP_TRY(hipEventCreate(&c.ev_run));
-        }
-        return 0;
-    });
-    runtime->d_alloc = now_seconds() - t0;
-    if (rc) return report("device allocation", rc);
-
-    // load (dpu_load, :541): code object, copy engines, and this shard's streams with their hardware queues
-    t0 = now_seconds();
-    rc = for_each_device(gpus, [&](int g) -> int {
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        if (int r = warm_up_device()) return r;
-        if (!sh[g].num_blocks) return 0;
-        PipelineStreams* ps = nullptr;
-        if (int r = pipeline_streams(devs.device_of(g), g, sh[g].chunks.size(), &ps)) return r;
-        sh[g].ps = *ps;
-        return 0;
-    });
-    runtime->load = now_seconds() - t0;
-    if (rc) return report("code object load", rc);
-
-    // the output buffer: the caller's (finite max) or ours, grown when a chunk does not fit
-    const bool caller_owned = output->buffer && output->max != ~0UL;
-    uint64_t capacity = caller_owned ? output->max : 0;
-    if (!caller_owned) {
-        capacity = 32 + input->length + input->length / 6;      // the reference's own bound (snappy_compress.c:446-449)
-        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, capacity);
-        if (!nbuf) {
-            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)capacity);
-            return SNAPPY_BUFFER_TOO_SMALL;
-        }
-        output->buffer = nbuf;
-    }
-    if (capacity < hdr_len) {
-        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the stream header\n", (unsigned long)capacity);
-        return SNAPPY_BUFFER_TOO_SMALL;
-    }
-    memcpy(output->buffer, hdr, hdr_len);
-    uint64_t total = hdr_len;
-    bool too_small = false;
-    // place chunk c of shard s at `total` and start its copy-out
-    auto copy_out_chunk = [&](CompressShard& s, CompressChunk& c) -> int {
-        const uint64_t body = c.stream_len - c.local_hdr;
-        c.out_off = total;
-        if (total + body > capacity) {
-            if (caller_owned) {
-                too_small = true;
-                total += body;
-                return 0;
-            }
-            // copies into the old buffer must land before it moves: every shard's copy-out stream, each on its own device
-            // (this runs either on shard 0's thread inside the pipeline or on the caller's thread after the join)
-            int here = 0;
-            HIP_TRY(hipGetDevice(&here));
-            for (int g2 = 0; g2 < gpus; ++g2) {
-                if (!sh[g2].num_blocks || !sh[g2].ps.out) continue;
-                HIP_TRY(hipSetDevice(devs.device_of(g2)));
-                HIP_TRY(hipStreamSynchronize(sh[g2].ps.out));
-            }
-            HIP_TRY(hipSetDevice(here));
-            capacity = std::max(total + body, capacity + capacity / 2);
-            uint8_t* nbuf = (uint8_t*)realloc(output->buffer, capacity);
-            if (!nbuf) return fail(SNAPPY_HIP_ERR_RUNTIME, "cannot grow the output buffer");
-            output->buffer = nbuf;
-        }
-        if (!too_small)
-            HIP_TRY(hipMemcpyAsync(output->buffer + c.out_off, c.d_stream + c.local_hdr, body, hipMemcpyDeviceToHost, s.ps.out));
-        total += body;
-        return 0;
-    };
-
-    // the pipeline (:547-704).  Shard 0 knows where its output goes and copies out as it runs; later shards learn their
-    // place once every earlier shard has reported its lengths, and copy out after the join.
-    t0 = now_seconds();
-    rc = for_each_device(gpus, [&](int g) -> int {
-        CompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        if (!s.num_blocks) return 0;
-        const size_t n = s.chunks.size();
-        auto copy_in = [&](size_t k) -> int {
-            CompressChunk& c = s.chunks[k];
-            HIP_TRY(hipMemcpyAsync(s.d_in + c.in_off, input->buffer + s.in_off + c.in_off, c.in_len, hipMemcpyHostToDevice, s.ps.in));
-            HIP_TRY(hipEventRecord(c.ev_in, s.ps.in));
-            return 0;
-        };
-        auto finish = [&](size_t k) -> int {
-            CompressChunk& c = s.chunks[k];
-            HIP_TRY(hipEventSynchronize(c.ev_run));
-            c.stream_len = s.ps.h_len[k];
-            return g == 0 ? copy_out_chunk(s, c) : 0;
-        };
-        HIP_TRY(hipEventRecord(s.ps.start, s.ps.in));
-        if (int r = copy_in(0)) return r;
-        for (size_t k = 0; k < n; ++k) {
-            CompressChunk& c = s.chunks[k];
-            // Two launches in flight, on alternating streams with a hash-table scratch each: a launch of one block per
-            // wavefront ends in a tail of half-empty CUs, which the next chunk's wavefronts fill.
-            hipStream_t run = (k & 1) ? s.ps.run2 : s.ps.run;
-            void* scratch = (k & 1) ? s.d_scratch2 : s.d_scratch;
-            HIP_TRY(hipStreamWaitEvent(run, c.ev_in, 0));
-            int r = snappy_hip_compress_blocks(s.d_in + c.in_off, c.in_len, block_size, s.d_slots + c.first_block * (uint64_t)stride,
-                                               stride, s.d_bytes + c.first_block, scratch, scratch_bytes, run);
-            if (r) return r;
-            // scan + gather on a stream of their own: small kernels that crawl beside the next chunk's K1 must not
-            // hold back the K1 launch after that
-            HIP_TRY(hipEventRecord(c.ev_k1, run));
-            HIP_TRY(hipStreamWaitEvent(s.ps.post, c.ev_k1, 0));
-            r = snappy_hip_compact(s.d_slots + c.first_block * (uint64_t)stride, stride, s.d_bytes + c.first_block, c.in_len, block_size,
-                                   c.d_stream, c.d_offsets, c.d_stream_len, s.ps.post);
-            if (r) return r;
-            HIP_TRY(hipMemcpyAsync(&s.ps.h_len[k], c.d_stream_len, sizeof(uint64_t), hipMemcpyDeviceToHost, s.ps.post));
-            HIP_TRY(hipEventRecord(c.ev_run, s.ps.post));
-            if (k + 1 < n)
-                if (int r2 = copy_in(k + 1)) return r2;
-            if (k >= 1)
-                if (int r2 = finish(k - 1)) return r2;
-        }
-        if (int r = finish(n - 1)) return r;
-        HIP_TRY(hipStreamSynchronize(s.ps.out));
-        HIP_TRY(hipEventElapsedTime(&s.exposed_in_ms, s.ps.start, s.chunks[0].ev_in));
-        HIP_TRY(hipEventElapsedTime(&s.kernel_ms, s.chunks[0].ev_in, s.chunks[n - 1].ev_run));
-        if (env_int("SNAPPY_HIP_PIPELINE_TRACE", 0))
-            for (size_t k = 0; k < n; ++k) {
-                float a = 0.f, b = 0.f, c = 0.f;
-                HIP_TRY(hipEventElapsedTime(&a, s.ps.start, s.chunks[k].ev_in));
-                HIP_TRY(hipEventElapsedTime(&b, s.ps.start, s.chunks[k].ev_k1));
-                HIP_TRY(hipEventElapsedTime(&c, s.ps.start, s.chunks[k].ev_run));
-                fprintf(stderr, "chunk %zu: copied in at %.2f ms, compressed at %.2f ms, framed at %.2f ms\n", k, a, b, c);
-            }
-        if (n >= 2) {                                   // the second-to-last launch runs on the other stream and may end later
-            float other = 0.f;
-            HIP_TRY(hipEventElapsedTime(&other, s.chunks[0].ev_in, s.chunks[n - 2].ev_run));
-            s.kernel_ms = std::max(s.kernel_ms, other);
-        }
-        return 0;
-    });
-    if (rc) return report("compress pipeline", rc);
-    if (gpus > 1) {
-        for (int g = 1; g < gpus && !rc; ++g) {
-            CompressShard& s = sh[g];
-            if (!s.num_blocks) continue;
-            if ((rc = (int)hipSetDevice(devs.device_of(g)))) break;
-            for (auto& c : s.chunks)
-                if ((rc = copy_out_chunk(s, c))) break;
-        }
-        if (!rc)
-            rc = for_each_device(gpus, [&](int g) -> int {
-                HIP_TRY(hipSetDevice(devs.device_of(g)));
-                if (g && sh[g].num_blocks) HIP_TRY(hipStreamSynchronize(sh[g].ps.out));
-                return 0;
-            });
-        if (rc) return report("device-to-host copy", rc);
-    }
-    const double wall = now_seconds() - t0;
-    shard_phase_times(sh, runtime, wall);
-
-    for (int g = 0; g < gpus; ++g)   // analogue of the per-tasklet log lines (dpu-compress/dpu_task.c:88)
-        printf("GPU %d: %f s, %lu bytes\n", g, sh[g].kernel_ms / 1000.0, (unsigned long)sh[g].in_len);
-
-    // free (dpu_free, :707)
-    t0 = now_seconds();
-    rc = for_each_device(gpus, [&](int g) -> int {
-        CompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        s.release();
-        return 0;
-    });
-    runtime->d_free = now_seconds() - t0;
-    if (rc) return report("free", rc);
-    if (too_small) {
-        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the %lu-byte stream\n", (unsigned long)output->max,
-                (unsigned long)total);
-        return SNAPPY_BUFFER_TOO_SMALL;
-    }
-    if (!caller_owned) {
-        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, total ? total : 1);
-        if (nbuf) output->buffer = nbuf;
-    }
-    output->length = total;
-    output->curr = output->buffer + total;
-    return SNAPPY_OK;
-}
-
-// Decompress counterpart: sizes are known from the host pre-scan, so the whole pipeline is enqueued without a host
-// round trip; chunk k's plaintext goes straight into its range of output->buffer (snappy_decompress.c:463).
-snappy_status decompress_pipelined(const uint8_t* buf, uint64_t in_total, struct host_buffer_context* output,
-                                   struct program_runtime* runtime, std::vector<DecompressShard>& sh, int gpus, const ShardDevices& devs,
-                                   uint32_t bs,
-                                   uint64_t total, uint64_t chunk_blocks)
-{
-    double t0 = now_seconds();
-    int rc = for_each_device(gpus, [&](int g) -> int {
-        DecompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        if (!s.num_blocks) return 0;
-        std::vector<BlockRange> ranges;
-        split_blocks(s.num_blocks, chunk_blocks, ranges);
-        for (auto& fb : ranges) {
-            DecompressChunk c;
-            c.first_block = fb.first;
-            c.num_blocks = fb.second;
-            c.out_off = c.first_block * bs;
-            c.out_len = std::min<uint64_t>(s.out_len - c.out_off, c.num_blocks * (uint64_t)bs);
-            HIP_TRY(hipEventCreate(&c.ev_in));
-            HIP_TRY(hipEventCreate(&c.ev_run));
-            s.chunks.push_back(c);
-        }
-        HIP_TRY(hipMalloc((void**)&s.d_stream, s.in_len + 16));
-        HIP_TRY(hipMalloc((void**)&s.d_boff, s.num_blocks * sizeof(uint64_t)));
-        HIP_TRY(hipMalloc((void**)&s.d_out, s.out_len + 16));
-        HIP_TRY(hipMalloc((void**)&s.d_status, s.num_blocks * sizeof(uint32_t)));
-        return 0;
-    });
-    runtime->d_alloc = now_seconds() - t0;
-    if (rc) return report("device allocation", rc);
-
-    t0 = now_seconds();
-    rc = for_each_device(gpus, [&](int g) -> int {
-        DecompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        if (int r = warm_up_device()) return r;
-        if (!s.num_blocks) return 0;
-        PipelineStreams* ps = nullptr;
-        if (int r = pipeline_streams(devs.device_of(g), g, s.num_blocks + 1, &ps)) return r;   // page-locked home of the block offsets
-        s.ps = *ps;
-        if (!s.rel_off.empty()) {                                           // chain already walked by the caller
-            memcpy(s.ps.h_len, s.rel_off.data(), s.num_blocks * sizeof(uint64_t));
-            s.ps.h_len[s.num_blocks] = s.in_len;
-            s.walked = s.num_blocks;
-            s.walk_at = s.in_off + s.in_len;
-        }
-        return 0;
-    });
-    runtime->load = now_seconds() - t0;
-    if (rc) return report("code object load", rc);
-
-    t0 = now_seconds();
-    rc = for_each_device(gpus, [&](int g) -> int {
-        DecompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        if (!s.num_blocks) return 0;
-        const size_t n = s.chunks.size();
-        const uint64_t* rel = s.ps.h_len;
-        auto copy_out = [&](size_t k) -> int {
-            DecompressChunk& c = s.chunks[k];
-            HIP_TRY(hipStreamWaitEvent(s.ps.out, c.ev_run, 0));
-            HIP_TRY(hipMemcpyAsync(output->buffer + s.out_off + c.out_off, s.d_out + c.out_off, c.out_len, hipMemcpyDeviceToHost, s.ps.out));
-            return 0;
-        };
-        HIP_TRY(hipEventRecord(s.ps.start, s.ps.in));
-        size_t issued = 0;
-        for (size_t k = 0; k < n; ++k) {
-            DecompressChunk& c = s.chunks[k];
-            // the host walks this chunk's part of the size chain while the previous chunk is still being copied in
-            if (!walk_chain(s, c.first_block + c.num_blocks, buf, in_total)) {
-                s.bad_chain = true;
-                break;
-            }
-            c.in_off = rel[c.first_block];
-            c.in_len = rel[c.first_block + c.num_blocks] - c.in_off;
-            HIP_TRY(hipMemcpyAsync(s.d_boff + c.first_block, rel + c.first_block, c.num_blocks * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                   s.ps.in));
-            HIP_TRY(hipMemcpyAsync(s.d_stream + c.in_off, buf + s.in_off + c.in_off, c.in_len, hipMemcpyHostToDevice, s.ps.in));
-            HIP_TRY(hipEventRecord(c.ev_in, s.ps.in));
-            HIP_TRY(hipStreamWaitEvent(s.ps.run, c.ev_in, 0));
-            // block i of the chunk is read at d_stream + d_boff[first + i] (offsets stay relative to the shard's slice)
-            int r = snappy_hip_decompress_blocks(s.d_stream, s.in_len, s.d_boff + c.first_block, c.out_len, bs, s.d_out + c.out_off,
-                                                 s.d_status + c.first_block, s.ps.run);
-            if (r) return r;
-            HIP_TRY(hipEventRecord(c.ev_run, s.ps.run));
-            ++issued;
-            if (k >= 1)
-                if (int r2 = copy_out(k - 1)) return r2;
-        }
-        if (!s.bad_chain && s.walk_at != s.in_off + s.in_len) s.bad_chain = true;    // the chain must end where the slice ends
-        if (issued && !s.bad_chain)
-            if (int r = copy_out(issued - 1)) return r;
-        HIP_TRY(hipStreamSynchronize(s.ps.in));
-        HIP_TRY(hipStreamSynchronize(s.ps.run));
-        HIP_TRY(hipStreamSynchronize(s.ps.out));
-        if (s.bad_chain || !issued) return 0;
-        std::vector<uint32_t> st(s.num_blocks);
-        HIP_TRY(hipMemcpy(st.data(), s.d_status, s.num_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < s.num_blocks; ++i)
-            if (st[i] != SNAPPY_HIP_BLOCK_OK) s.bad = true;
-        HIP_TRY(hipEventElapsedTime(&s.exposed_in_ms, s.ps.start, s.chunks[0].ev_in));
-        HIP_TRY(hipEventElapsedTime(&s.kernel_ms, s.chunks[0].ev_in, s.chunks[n - 1].ev_run));
-        return 0;
-    });
-    const double wall = now_seconds() - t0;
-    if (rc) return report("decompress pipeline", rc);
-    shard_phase_times(sh, runtime, wall);
-
-    for (int g = 0; g < gpus; ++g)
-        printf("GPU %d: %f s, %lu bytes\n", g, sh[g].kernel_ms / 1000.0, (unsigned long)sh[g].in_len);
-
-    t0 = now_seconds();
-    rc = for_each_device(gpus, [&](int g) -> int {
-        DecompressShard& s = sh[g];
-        HIP_TRY(hipSetDevice(devs.device_of(g)));
-        s.release();
-        return 0;
-    });
-    runtime->d_free = now_seconds() - t0;
-    if (rc) return report("free", rc);
-    for (auto& s : sh) {
-        if (s.bad_chain) {
-            fprintf(stderr, "snappy_hip: size chain leaves the stream (block %lu of %lu)\n",
-                    (unsigned long)(s.first_block + s.walked), (unsigned long)(s.first_block + s.num_blocks));
-            return SNAPPY_INVALID_INPUT;
-        }
-        if (s.bad) {
-            fprintf(stderr, "snappy_hip: malformed block in the stream\n");
-            return SNAPPY_INVALID_INPUT;
-        }
-    }
-    output->curr = output->buffer + total;
-    return SNAPPY_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-static snappy_status compress_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
-                                       struct program_runtime* runtime)
-{
-    double t0 = now_seconds();
-    if (!input || !output || !runtime) return SNAPPY_INVALID_INPUT;
-    if (input->length && !input->buffer) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
-    if (!block_size_ok(block_size)) {
-        fprintf(stderr, "snappy_hip: block size %u is outside 1..65535 (16-bit hash table entries)\n", block_size);
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (input->length > 0xffffffffull) {
-        fprintf(stderr, "snappy_hip: input of %lu bytes does not fit the format's uint32 length\n", input->length);
-        return SNAPPY_BUFFER_TOO_SMALL;
-    }
-    const uint64_t n = input->length;
-    const uint64_t nb = snappy_hip_num_blocks(n, block_size);
-    const ShardDevices devs = requested_devices();
-    int gpus = devs.shards;
-    if (gpus <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    if ((uint64_t)gpus > nb) gpus = nb ? (int)nb : 1;
-
-    // partition: contiguous block ranges per device (snappy_compress.c:494-520)
-    const uint64_t per = nb ? (nb + gpus - 1) / gpus : 0;
-    std::vector<CompressShard> sh(gpus);
-    CompressCleanup cleanup{sh, devs};
-    for (int g = 0; g < gpus; ++g) {
-        sh[g].first_block = (uint64_t)g * per;
-        const uint64_t last = std::min(nb, sh[g].first_block + per);
-        sh[g].num_blocks = last > sh[g].first_block ? last - sh[g].first_block : 0;
-        sh[g].in_off = sh[g].first_block * block_size;
-        sh[g].in_len = sh[g].num_blocks ? std::min<uint64_t>(n - sh[g].in_off, sh[g].num_blocks * (uint64_t)block_size) : 0;
-    }
-    uint8_t hdr[10];
-    const uint32_t hdr_len = snappy_hip_write_header(hdr, (uint32_t)n, block_size);   // :523-525
-    const uint32_t stride = snappy_hip_slot_stride(block_size);
-    runtime->pre += now_seconds() - t0;
-    // One code path: a shard is a list of chunks; SNAPPY_HIP_PIPELINE_BLOCKS=0 (or a small shard) makes it one chunk, which
-    // is the strictly phased copy-in / run / copy-out of the reference (snappy_compress.c:547-704).
-    uint64_t chunk_blocks = pipeline_chunk_blocks(per, block_size);
-    if (!chunk_blocks || per <= chunk_blocks) chunk_blocks = std::max<uint64_t>(per, 1);
-    return compress_pipelined(input, output, block_size, runtime, sh, gpus, devs, hdr, hdr_len, stride, chunk_blocks);
-}
-
-static snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output,
-                                         struct program_runtime* runtime)
-{
-    double t0 = now_seconds();
-    if (!input || !output || !runtime) return SNAPPY_INVALID_INPUT;
-    if (!input->buffer || !input->curr || input->curr < input->buffer) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
-
-    // block-size varint (snappy_decompress.c:298-303)
-    const uint8_t* const buf = input->buffer;
-    const uint64_t in_total = input->length;
-    uint64_t at = (uint64_t)(input->curr - input->buffer);
-    uint32_t bs = 0;
-    const uint32_t used = (at <= in_total) ? get_varint32(buf + at, in_total - at, &bs) : 0;
-    if (!used) {
-        fprintf(stderr, "Failed to read decompressed block size\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    at += used;
-    input->curr += used;
-    const uint64_t total = output->length;
-    if (total == 0) {
-        runtime->pre += now_seconds() - t0;
-        return (at == in_total) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
-    }
-    if (!block_size_ok(bs)) {
-        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (!output->buffer) {
-        fprintf(stderr, "snappy_hip: output->buffer is NULL (setup_decompression allocates it, snappy_decompress.c:207-209)\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    const uint64_t nb = snappy_hip_num_blocks(total, bs);
-    // the header is untrusted: every block needs at least its u32 size prefix, so a stream of in_total - at bytes cannot
-    // hold more than (in_total - at) / 4 blocks -- checked before anything is sized by nb
-    if (nb > (in_total - at) / 4) {
-        fprintf(stderr, "snappy_hip: header promises %lu blocks, the stream has room for %lu\n", (unsigned long)nb,
-                (unsigned long)((in_total - at) / 4));
-        return SNAPPY_INVALID_INPUT;
-    }
-    const ShardDevices devs = requested_devices();
-    int gpus = devs.shards;
-    if (gpus <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    if ((uint64_t)gpus > nb) gpus = (int)nb;
-    // A decode launch takes about as long for 2048 blocks as for 8192 (one block per wavefront either way), so the
-    // overlapped form pays from three chunks per shard upwards.
-    const uint64_t chunk_blocks = pipeline_chunk_blocks((nb + gpus - 1) / gpus, bs);
-    const bool overlapped = chunk_blocks && (nb + gpus - 1) / gpus >= 3 * chunk_blocks;
-    if (overlapped && gpus == 1) {
-        // one shard: the host walks the size chain chunk by chunk inside the pipeline instead of up front
-        std::vector<DecompressShard> one(1);
-        DecompressCleanup cleanup{one, devs};
-        one[0].num_blocks = nb;
-        one[0].in_off = one[0].walk_at = at;
-        one[0].in_len = in_total - at;
-        one[0].out_len = total;
-        runtime->pre += now_seconds() - t0;
-        return decompress_pipelined(buf, in_total, output, runtime, one, 1, devs, bs, total, chunk_blocks);
-    }
-    // host pre-scan of the size chain (:306-341): the blocks are split over the devices before anything is copied, so every
-    // offset is needed first.  In parallel shares where the stream is long enough (csrc/host_chain.hpp: exact by
-    // construction, ~7 ms per GiB of serial pointer chase otherwise -- the whole of `pre`, and it does not shrink with the
-    // number of devices); SNAPPY_HIP_HOST_WALK_THREADS=1 is the serial walk alone, which also names a damaged stream's fault.
-    std::vector<uint64_t> off;
-    const unsigned walk_threads = (unsigned)std::max(1, env_int("SNAPPY_HIP_HOST_WALK_THREADS",
-                                                               (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
-    if (!host_chain::parallel_walk(buf, in_total, at, nb, bs, walk_threads, off)) {
-        off.assign(nb + 1, 0);
-        for (uint64_t i = 0; i < nb; ++i) {
-            if (at + 4 > in_total) {
-                fprintf(stderr, "snappy_hip: truncated stream (block %lu of %lu)\n", (unsigned long)i, (unsigned long)nb);
-                return SNAPPY_INVALID_INPUT;
-            }
-            off[i] = at;
-            at += 4 + (uint64_t)le32_host(buf + at);
-        }
-        off[nb] = at;
-        if (at != in_total) {
-            fprintf(stderr, "snappy_hip: size chain ends at %lu, stream has %lu bytes\n", (unsigned long)at, (unsigned long)in_total);
-            return SNAPPY_INVALID_INPUT;
-        }
-    }
-    const uint64_t per = (nb + gpus - 1) / gpus;
-    std::vector<DecompressShard> sh(gpus);
-    DecompressCleanup cleanup{sh, devs};
-    for (int g = 0; g < gpus; ++g) {
-        DecompressShard& s = sh[g];
-        s.first_block = (uint64_t)g * per;
-        const uint64_t last = std::min(nb, s.first_block + per);
-        s.num_blocks = last > s.first_block ? last - s.first_block : 0;
-        if (!s.num_blocks) continue;
-        s.in_off = off[s.first_block];
-        s.in_len = off[last] - s.in_off;
-        s.out_off = s.first_block * bs;
-        s.out_len = std::min<uint64_t>(total - s.out_off, s.num_blocks * (uint64_t)bs);
-        s.rel_off.resize(s.num_blocks);
-        for (uint64_t i = 0; i < s.num_blocks; ++i) s.rel_off[i] = off[s.first_block + i] - s.in_off;
-    }
-    runtime->pre += now_seconds() - t0;
-    // one chunk per shard = the strictly phased form (the size chain was walked above, in `pre`)
-    return decompress_pipelined(buf, in_total, output, runtime, sh, gpus, devs, bs, total, overlapped ? chunk_blocks : std::max<uint64_t>(per, 1));
-}
-
-// The exported pair: one call at a time per process (the cached pipeline streams and their page-locked scratch are per
-// process; the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618), the caller's
-// current HIP device restored on every return path, and no C++ exception crosses the C boundary.
-snappy_status snappy_compress_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
-                                  struct program_runtime* runtime)
-{
-    try {
-        std::lock_guard<std::mutex> one_at_a_time(*pipeline_mutex());
-        CallerDevice keep;
-        return compress_gpu_body(input, output, block_size, runtime);
-    } catch (const std::bad_alloc&) {
-        fprintf(stderr, "snappy_hip: out of host memory\n");
-        return SNAPPY_BUFFER_TOO_SMALL;
-    } catch (const std::exception& e) {
-        fprintf(stderr, "snappy_hip: %s\n", e.what());
-        return SNAPPY_INVALID_INPUT;
-    } catch (...) {
-        return SNAPPY_INVALID_INPUT;
-    }
-}
-
-snappy_status snappy_decompress_gpu(struct host_buffer_context* input, struct host_buffer_context* output,
-                                    struct program_runtime* runtime)
-{
-    try {
-        std::lock_guard<std::mutex> one_at_a_time(*pipeline_mutex());
-        CallerDevice keep;
-        return decompress_gpu_body(input, output, runtime);
-    } catch (const std::bad_alloc&) {
-        fprintf(stderr, "snappy_hip: out of host memory\n");
-        return SNAPPY_BUFFER_TOO_SMALL;
-    } catch (const std::exception& e) {
-        fprintf(stderr, "snappy_hip: %s\n", e.what());
-        return SNAPPY_INVALID_INPUT;
-    } catch (...) {
-        return SNAPPY_INVALID_INPUT;
-    }
-}
-
 #ifdef SNAPPY_PAIR_PROBE
 int snappy_hip_debug_pair_prof(unsigned long long* out, int reset)
 {
@@ -1744,3 +855,5 @@ int snappy_hip_debug_pair_prof(unsigned long long* out, int reset)
 #endif
 
 }  // extern "C"
+
+#include "dropin_pair.hpp"

@@ -125,7 +125,7 @@ def num_blocks(n, block_size):
 
 def shard_block_range(num_blocks_total, shards, shard):
     """(first_block, block_count) of `shard` when a file of `num_blocks_total` blocks is split over `shards` devices: the
-    contiguous ranges of ceil(B / G) blocks that snappy_compress_gpu / snappy_decompress_gpu use (csrc/snappy_hip.hip),
+    contiguous ranges of ceil(B / G) blocks that snappy_compress_gpu / snappy_decompress_gpu use (csrc/dropin_plan.hpp),
     i.e. the partitioning of the reference's input_blocks_per_dpu (snappy_compress.c:494-520)."""
     per = (num_blocks_total + shards - 1) // shards if num_blocks_total else 0
     first = min(num_blocks_total, shard * per)

@@ -1,0 +1,278 @@
+"""csrc/dropin_plan.hpp -- where the drop-in pair puts every byte (plain C++, compiled here with g++): the shard partition,
+the pipeline chunks of each direction, the compress pools and the serial walk of the size chain.  The chunkings the pair
+has always used are pinned, and the walker must give the oracle's offsets and stop at the right block of a damaged stream
+without reading beyond it (the driver ends the stream at an inaccessible page)."""
+import os
+import subprocess
+
+import pytest
+
+import datagen
+import oracle_lib as oracle
+import snappy_hip_binding as shb
+from conftest import golden_bytes
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pim-compression_amd", "csrc")
+
+DRIVER = r'''
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <sys/mman.h>
+#include "dropin_plan.hpp"
+using namespace dropin_plan;
+static void print_chunks(const char* dir, const std::vector<Range>& shards, uint64_t chunk, int walk, uint32_t bs) {
+    // per non-empty shard: (chunks, blocks of the first chunk, blocks of the last); exit 3 unless the chunks tile the shard
+    printf("%s walk=%d", dir, walk);
+    for (const Range& s : shards) {
+        if (!s.num_blocks) continue;
+        const std::vector<Range> c = split_blocks(s.num_blocks, s.plain_len, bs, chunk);
+        uint64_t b = 0, o = 0;
+        for (size_t i = 0; i < c.size(); ++i) {
+            if (c[i].first_block != b || c[i].plain_off != o || !c[i].num_blocks) exit(3);
+            if (i + 1 < c.size() && (c[i].num_blocks % 16 || c[i].num_blocks != c[0].num_blocks)) exit(3);
+            if (c[i].plain_off % 16 || c[i].plain_len != std::min<uint64_t>(s.plain_len - o, c[i].num_blocks * bs)) exit(3);
+            b += c[i].num_blocks;
+            o += c[i].plain_len;
+        }
+        if (b != s.num_blocks || o != s.plain_len) exit(3);
+        printf(" (%zu,%lu,%lu)", c.size(), (unsigned long)c[0].num_blocks, (unsigned long)c.back().num_blocks);
+    }
+    printf("\n");
+}
+int main(int argc, char** argv) {
+    const std::string mode = argv[1];
+    if (mode == "part") {            // part <nb> <want> <total> <bs>
+        const uint64_t nb = strtoull(argv[2], 0, 10), total = strtoull(argv[4], 0, 10);
+        const int shards = shard_count(atoi(argv[3]), nb);
+        printf("%d", shards);
+        for (const Range& s : partition(nb, shards, total, (uint32_t)atoi(argv[5])))
+            printf(" %lu,%lu,%lu,%lu", (unsigned long)s.first_block, (unsigned long)s.num_blocks, (unsigned long)s.plain_off,
+                   (unsigned long)s.plain_len);
+        printf("\n");
+    } else if (mode == "plan") {     // plan <bytes> <bs> <want> [SNAPPY_HIP_PIPELINE_BLOCKS]: both directions' chunkings
+        const uint64_t n = strtoull(argv[2], 0, 10);
+        const uint32_t bs = (uint32_t)atoi(argv[3]);
+        const char* knob = argc > 5 ? argv[5] : nullptr;
+        const uint64_t nb = (n + bs - 1) / bs;
+        const int shards = shard_count(atoi(argv[4]), nb);
+        const uint64_t per = shard_blocks(nb, shards);
+        print_chunks("C", partition(nb, shards, n, bs), compress_chunk_blocks(per, pipeline_chunk_blocks(per, bs, knob)), 0, bs);
+        const DecompressChunking d = decompress_chunking(per, pipeline_chunk_blocks(per, bs, knob), shards);
+        print_chunks("D", partition(nb, shards, n, bs), d.chunk_blocks, d.walk_in_pipeline, bs);
+    } else if (mode == "layout") {   // layout <nb> <plain_len> <bs> <stride> <chunk>
+        const CompressLayout l = compress_layout(strtoull(argv[2], 0, 10), strtoull(argv[3], 0, 10), (uint32_t)atoi(argv[4]),
+                                                 (uint32_t)atoi(argv[5]), strtoull(argv[6], 0, 10));
+        printf("%lu %lu\n", (unsigned long)l.stream_pool, (unsigned long)l.offsets_pool);
+        for (const CompressChunk& c : l.chunks)
+            printf("%lu %lu %lu %lu %u %lu %lu\n", (unsigned long)c.first_block, (unsigned long)c.num_blocks, (unsigned long)c.plain_off,
+                   (unsigned long)c.plain_len, c.local_hdr, (unsigned long)c.stream_at, (unsigned long)c.offsets_at);
+    } else {                         // walk|whole <file> <first> <nb> <step>: the walk `step` blocks at a time, as the pipeline
+                                     // does; `whole` prints whole_walk_error of the walk instead
+        FILE* f = fopen(argv[2], "rb"); if (!f) return 2;
+        fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
+        const size_t page = 4096, mapped = ((n + page - 1) / page + 1) * page;
+        uint8_t* base = (uint8_t*)mmap(nullptr, mapped, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        mprotect(base + mapped - page, page, PROT_NONE);
+        uint8_t* buf = base + mapped - page - n;
+        if (n && fread(buf, 1, n, f) != (size_t)n) return 2;
+        const uint64_t first = strtoull(argv[3], 0, 10), nb = strtoull(argv[4], 0, 10), step = strtoull(argv[5], 0, 10);
+        std::vector<uint64_t> rel(nb + 1, ~0ull);
+        Walk w{0, first};
+        for (uint64_t upto = std::min(step, nb); w.stop == kDone; upto = std::min(upto + step, nb)) {
+            w = walk_chain(buf, (uint64_t)n, first, rel.data(), w, upto);
+            if (upto == nb) break;
+        }
+        if (mode == "whole") {
+            printf("[%s]\n", whole_walk_error(w, nb, (uint64_t)n).c_str());
+            return 0;
+        }
+        printf("%d %lu %lu", (int)w.stop, (unsigned long)w.block, (unsigned long)w.at);
+        for (uint64_t i = 0; i <= w.block && i <= nb; ++i) printf(" %lu", (unsigned long)rel[i]);
+        printf("\n");
+    }
+    return 0;
+}
+'''
+
+# The chunkings of the code before the plan was split out of snappy_hip.hip, per direction: "walk=1" = the one shard walks
+# the size chain inside its pipeline; per non-empty shard (chunks, blocks of the first chunk, blocks of the last chunk).
+# Lines: bytes, block size, shards, SNAPPY_HIP_PIPELINE_BLOCKS ("default" = unset).
+PINNED = """
+268435456 32768 1 default | C walk=0 (4,2048,2048) | D walk=1 (4,2048,2048)
+268435456 32768 1 0 | C walk=0 (1,8192,8192) | D walk=0 (1,8192,8192)
+268435456 32768 1 8 | C walk=0 (512,16,16) | D walk=1 (512,16,16)
+268435456 32768 1 16 | C walk=0 (512,16,16) | D walk=1 (512,16,16)
+268435456 32768 1 32 | C walk=0 (256,32,32) | D walk=1 (256,32,32)
+268435456 32768 1 1024 | C walk=0 (8,1024,1024) | D walk=1 (8,1024,1024)
+268435456 32768 3 default | C walk=0 (2,1376,1355) (2,1376,1355) (2,1376,1354) | D walk=0 (1,2731,2731) (1,2731,2731) (1,2730,2730)
+268435456 32768 3 0 | C walk=0 (1,2731,2731) (1,2731,2731) (1,2730,2730) | D walk=0 (1,2731,2731) (1,2731,2731) (1,2730,2730)
+268435456 32768 3 8 | C walk=0 (171,16,11) (171,16,11) (171,16,10) | D walk=0 (171,16,11) (171,16,11) (171,16,10)
+268435456 32768 3 16 | C walk=0 (171,16,11) (171,16,11) (171,16,10) | D walk=0 (171,16,11) (171,16,11) (171,16,10)
+268435456 32768 3 32 | C walk=0 (86,32,11) (86,32,11) (86,32,10) | D walk=0 (86,32,11) (86,32,11) (86,32,10)
+268435456 32768 3 1024 | C walk=0 (3,912,907) (3,912,907) (3,912,906) | D walk=0 (1,2731,2731) (1,2731,2731) (1,2730,2730)
+1073741824 32768 1 default | C walk=0 (8,4096,4096) | D walk=1 (8,4096,4096)
+1073741824 32768 1 0 | C walk=0 (1,32768,32768) | D walk=0 (1,32768,32768)
+1073741824 32768 1 8 | C walk=0 (2048,16,16) | D walk=1 (2048,16,16)
+1073741824 32768 1 16 | C walk=0 (2048,16,16) | D walk=1 (2048,16,16)
+1073741824 32768 1 32 | C walk=0 (1024,32,32) | D walk=1 (1024,32,32)
+1073741824 32768 1 1024 | C walk=0 (32,1024,1024) | D walk=1 (32,1024,1024)
+1073741824 32768 3 default | C walk=0 (4,2736,2715) (4,2736,2715) (4,2736,2714) | D walk=0 (4,2736,2715) (4,2736,2715) (4,2736,2714)
+1073741824 32768 3 0 | C walk=0 (1,10923,10923) (1,10923,10923) (1,10922,10922) | D walk=0 (1,10923,10923) (1,10923,10923) (1,10922,10922)
+1073741824 32768 3 8 | C walk=0 (683,16,11) (683,16,11) (683,16,10) | D walk=0 (683,16,11) (683,16,11) (683,16,10)
+1073741824 32768 3 16 | C walk=0 (683,16,11) (683,16,11) (683,16,10) | D walk=0 (683,16,11) (683,16,11) (683,16,10)
+1073741824 32768 3 32 | C walk=0 (342,32,11) (342,32,11) (342,32,10) | D walk=0 (342,32,11) (342,32,11) (342,32,10)
+1073741824 32768 3 1024 | C walk=0 (11,1008,843) (11,1008,843) (11,1008,842) | D walk=0 (11,1008,843) (11,1008,843) (11,1008,842)
+3221225472 32768 1 default | C walk=0 (24,4096,4096) | D walk=1 (24,4096,4096)
+3221225472 32768 1 0 | C walk=0 (1,98304,98304) | D walk=0 (1,98304,98304)
+3221225472 32768 1 8 | C walk=0 (6144,16,16) | D walk=1 (6144,16,16)
+3221225472 32768 1 16 | C walk=0 (6144,16,16) | D walk=1 (6144,16,16)
+3221225472 32768 1 32 | C walk=0 (3072,32,32) | D walk=1 (3072,32,32)
+3221225472 32768 1 1024 | C walk=0 (96,1024,1024) | D walk=1 (96,1024,1024)
+3221225472 32768 3 default | C walk=0 (8,4096,4096) (8,4096,4096) (8,4096,4096) | D walk=0 (8,4096,4096) (8,4096,4096) (8,4096,4096)
+3221225472 32768 3 0 | C walk=0 (1,32768,32768) (1,32768,32768) (1,32768,32768) | D walk=0 (1,32768,32768) (1,32768,32768) (1,32768,32768)
+3221225472 32768 3 8 | C walk=0 (2048,16,16) (2048,16,16) (2048,16,16) | D walk=0 (2048,16,16) (2048,16,16) (2048,16,16)
+3221225472 32768 3 16 | C walk=0 (2048,16,16) (2048,16,16) (2048,16,16) | D walk=0 (2048,16,16) (2048,16,16) (2048,16,16)
+3221225472 32768 3 32 | C walk=0 (1024,32,32) (1024,32,32) (1024,32,32) | D walk=0 (1024,32,32) (1024,32,32) (1024,32,32)
+3221225472 32768 3 1024 | C walk=0 (32,1024,1024) (32,1024,1024) (32,1024,1024) | D walk=0 (32,1024,1024) (32,1024,1024) (32,1024,1024)
+1073741824 4096 1 default | C walk=0 (8,32768,32768) | D walk=1 (8,32768,32768)
+1073741824 4096 1 0 | C walk=0 (1,262144,262144) | D walk=0 (1,262144,262144)
+1073741824 4096 1 8 | C walk=0 (16384,16,16) | D walk=1 (16384,16,16)
+1073741824 4096 1 16 | C walk=0 (16384,16,16) | D walk=1 (16384,16,16)
+1073741824 4096 1 32 | C walk=0 (8192,32,32) | D walk=1 (8192,32,32)
+1073741824 4096 1 1024 | C walk=0 (256,1024,1024) | D walk=1 (256,1024,1024)
+1073741824 4096 3 default | C walk=0 (4,21856,21814) (4,21856,21814) (4,21856,21812) | D walk=0 (4,21856,21814) (4,21856,21814) (4,21856,21812)
+1073741824 4096 3 0 | C walk=0 (1,87382,87382) (1,87382,87382) (1,87380,87380) | D walk=0 (1,87382,87382) (1,87382,87382) (1,87380,87380)
+1073741824 4096 3 8 | C walk=0 (5462,16,6) (5462,16,6) (5462,16,4) | D walk=0 (5462,16,6) (5462,16,6) (5462,16,4)
+1073741824 4096 3 16 | C walk=0 (5462,16,6) (5462,16,6) (5462,16,4) | D walk=0 (5462,16,6) (5462,16,6) (5462,16,4)
+1073741824 4096 3 32 | C walk=0 (2731,32,22) (2731,32,22) (2731,32,20) | D walk=0 (2731,32,22) (2731,32,22) (2731,32,20)
+1073741824 4096 3 1024 | C walk=0 (86,1024,342) (86,1024,342) (86,1024,340) | D walk=0 (86,1024,342) (86,1024,342) (86,1024,340)
+"""
+
+DONE, TRUNCATED, LEAVES = 0, 1, 2
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def driver(request, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("dropin_plan_" + request.param)
+    src = tmp / "d.cpp"
+    src.write_text(DRIVER)
+    exe = tmp / "d"
+    flags = ["-O2"] if request.param == "plain" else ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror"] + flags + ["-I", CSRC, str(src), "-o", str(exe)])
+
+    def run(*args):
+        r = subprocess.run([str(exe)] + [str(a) for a in args], capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+        assert r.returncode == 0, (args, r.returncode, r.stderr[-2000:])
+        return r.stdout
+    run.tmp = tmp
+    return run
+
+
+def test_partition_matches_binding(driver):
+    for nb in (0, 1, 15, 16, 17, 4097, 32768, 98304):
+        for want in range(1, 9):
+            bs, total = 32768, nb * 32768 - (nb > 0) * 1234
+            out = driver("part", nb, want, total, bs).split()
+            shards = int(out[0])
+            assert shards == (want if want <= nb else (nb if nb else 1))             # the clamp: no more shards than blocks
+            assert len(out) == shards + 1
+            for g, field in enumerate(out[1:]):
+                first, num, off, length = map(int, field.split(","))
+                assert (first, num) == shb.shard_block_range(nb, shards, g), (nb, want, g)
+                if num:
+                    assert off == first * bs and length == min(total - off, num * bs)
+                else:
+                    assert (off, length) == (0, 0)
+
+
+def test_chunkings_are_pinned(driver):
+    for line in PINNED.strip().splitlines():
+        args, want_c, want_d = [p.strip() for p in line.split("|")]
+        n, bs, shards, knob = args.split()
+        out = driver("plan", n, bs, shards, *([] if knob == "default" else [knob])).strip().splitlines()
+        assert out == [want_c, want_d], args
+
+
+def test_chunks_tile_every_shard(driver):
+    # (the driver exits 3 unless the chunks tile the shard, 16-block multiples but the last, slices 16-byte aligned)
+    for bs in (1, 4, 7, 1000, 4097, 32768, 65535):
+        for n in (1, bs * 16 - 1, bs * 4097 + 3, min(50_000_017, bs * 100_003)):
+            for shards in (1, 3, 5):
+                for knob in ("8", "16", "33", "1024", None):
+                    driver("plan", n, bs, shards, *([knob] if knob else []))
+
+
+def test_compress_pools(driver):
+    for bs in (1, 4, 7, 1000, 4097, 32768, 65535):
+        stride = shb.slot_stride(bs)
+        for nb, tail in ((1, 1), (17, bs), (4097, max(1, bs // 3)), (10_000, bs)):
+            plain_len = (nb - 1) * bs + tail
+            for chunk in (16, 48, 1024, 8192):
+                lines = driver("layout", nb, plain_len, bs, stride, chunk).split("\n")
+                stream_pool, offsets_pool = map(int, lines[0].split())
+                chunks = [tuple(map(int, ln.split())) for ln in lines[1:] if ln]
+                at_s = at_o = 0
+                for first, num, off, length, hdr, stream_at, offsets_at in chunks:
+                    assert stream_at == at_s and offsets_at == at_o and stream_at % 256 == 0 and offsets_at % 256 == 0
+                    assert hdr == len(shb.write_header(length, bs))
+                    bound = shb.lib().snappy_hip_stream_bound(length, bs)
+                    at_s += (bound + 255) // 256 * 256                   # no overlap: each chunk owns its padded bound
+                    at_o += ((num + 1) * 8 + 255) // 256 * 256
+                assert (stream_pool, offsets_pool) == (at_s, at_o)
+                assert sum(c[1] for c in chunks) == nb and sum(c[3] for c in chunks) == plain_len
+
+
+def _serial_loop_message(stream, at, nb):
+    """The up-front serial walk that whole_walk_error replaced, with its two messages."""
+    for i in range(nb):
+        if at + 4 > len(stream):
+            return f"truncated stream (block {i} of {nb})"
+        at += 4 + int.from_bytes(stream[at:at + 4], "little")
+    return "" if at == len(stream) else f"size chain ends at {at}, stream has {len(stream)} bytes"
+
+
+def _walk(driver, stream, first, nb, step):
+    p = driver.tmp / "s.bin"
+    p.write_bytes(stream)
+    out = [int(v) for v in driver("walk", p, first, nb, step).split()]
+    return out[0], out[1], out[2], out[3:]
+
+
+def test_walker_on_goldens_and_damaged_streams(driver):
+    streams = [golden_bytes(n + ".snappy") for n in ("alice", "coding", "terror2", "plrabn12", "world192", "xml")]
+    streams.append(oracle.compress(datagen.text_random_interleave(golden_bytes("plrabn12.txt"), 300_007), 1000))
+    for stream in streams:
+        total, bs, hdr = oracle.read_header(stream)
+        nb = (total + bs - 1) // bs
+        offs = [int(v) - hdr for v in oracle.index_blocks(stream)]
+        for step in (1, 16, nb):
+            stop, block, at, rel = _walk(driver, stream, hdr, nb, step)
+            assert (stop, block, at) == (DONE, nb, len(stream)) and rel == offs + [len(stream) - hdr]
+        # truncated inside the last block's body: that block leaves the stream
+        stop, block, at, rel = _walk(driver, stream[:-1], hdr, nb, 16)
+        assert (stop, block, at) == (LEAVES, nb - 1, len(stream)) and rel[:nb - 1] == offs[:nb - 1]
+        # cut inside the last block's size prefix
+        last = hdr + offs[-1]
+        stop, block, _, _ = _walk(driver, stream[:last + 2], hdr, nb, 16)
+        assert (stop, block) == (TRUNCATED, nb - 1)
+        # overlong: the chain ends before the stream does (the caller then compares `at` with the stream's end)
+        stop, block, at, _ = _walk(driver, stream + b"\0" * 7, hdr, nb, 16)
+        assert (stop, block, at) == (DONE, nb, len(stream))
+        # a size field of a middle block sends the chain out of the buffer
+        mid = nb // 2
+        b = bytearray(stream)
+        b[hdr + offs[mid]:hdr + offs[mid] + 4] = (0x7ffffff0).to_bytes(4, "little")
+        stop, block, at, rel = _walk(driver, bytes(b), hdr, nb, 16)
+        assert (stop, block, at) == (LEAVES, mid, hdr + offs[mid] + 4 + 0x7ffffff0) and rel[:mid + 1] == offs[:mid + 1]
+        # the up-front walk's messages are those of the serial loop it replaced, for every kind of damage
+        damaged = [stream, stream[:-1], stream[:last + 2], stream[:last], stream + b"\0" * 7, bytes(b), stream[:hdr + 3]]
+        b2 = bytearray(stream)
+        b2[hdr + offs[-1]:hdr + offs[-1] + 4] = (0x7ffffff0).to_bytes(4, "little")       # the last block leaves
+        damaged.append(bytes(b2))
+        for bad in damaged:
+            p = driver.tmp / "s.bin"
+            p.write_bytes(bad)
+            assert driver("whole", p, hdr, nb, nb).strip() == "[%s]" % _serial_loop_message(bad, hdr, nb)
