@@ -254,6 +254,63 @@ struct snappy_hip_decompress_item {
 SNAPPY_HIP_API int snappy_hip_decompress_blocks_batch(const struct snappy_hip_decompress_item *items, uint32_t count, uint32_t block_size,
                                        void *stream);
 
+/*
+ * Byte ranges of framed containers, decoded without the rest of them.  Range i asks for uncompressed bytes
+ * [offset, offset + length) of container d_descs[stream] and gets them at dst.  Only the blocks a range touches are decoded:
+ * a block wholly inside the range in place in dst, the first and last block of the range -- when only part of them is
+ * wanted -- into a slot of d_scratch, from which the wanted bytes are copied to dst.
+ *
+ * d_descs: device array of `count` snappy_hip_stream_desc, with stream, stream_len, block_offsets (num_blocks entries, as
+ *   snappy_hip_index_streams or snappy_hip_compact leave them), total_len, block_size and num_blocks filled in (result is
+ *   not read).  Containers may have different block sizes, none above max_block_size.
+ * d_ranges, d_status: device arrays of range_count entries, so that ranges can be produced on the device.
+ * d_status[i] (written by the call):
+ *   SNAPPY_HIP_BLOCK_OK             iff every block the range touches would be OK in snappy_hip_decompress_blocks (strict:
+ *                                   every touched block is decoded in full, even when only part of it is wanted);
+ *   SNAPPY_HIP_BLOCK_INVALID        otherwise; the contents of dst are then unspecified;
+ *   SNAPPY_HIP_RANGE_OUT_OF_BOUNDS  a malformed request: stream >= count, offset + length > total_len or overflowing, a
+ *                                   container whose block size is 0 or above max_block_size or whose num_blocks is too small
+ *                                   for the range, a null dst with length > 0, or a range whose pieces lie beyond the
+ *                                   2^31st of the call (a piece = one block of one range).  Nothing is written to its dst.
+ * A range of length 0 is OK and writes nothing.  Nothing outside [dst, dst + length) of any range is ever written, whatever
+ * the streams hold; ranges may overlap in their containers, not in their destinations.
+ *
+ * d_scratch: 256-byte aligned device workspace, not shared with a launch that runs concurrently; contents need not be
+ * initialised.  It holds the ranges' piece prefix (range_count + 2 u64, rounded up to 256 bytes) and then one slot of
+ * max_block_size bytes, rounded up to 256, per wavefront.  The pieces are counted on the device, so the grid is K2's for an
+ * unbounded count -- one wavefront per wavefront slot of the current device, SNAPPY_HIP_K2_WAVES caps it -- or the number of
+ * slots the scratch holds, whichever is smaller; a scratch too small for one slot is SNAPPY_HIP_ERR_ARG.  snappy_hip_decompress_ranges_scratch_bytes returns the size for
+ * the full grid on the current device (e.g. 256 MiB + prefix for 32 KiB blocks on a whole MI355X); less only means
+ * fewer wavefronts.
+ * The call only enqueues work on `stream`; it never synchronises.
+ */
+#define SNAPPY_HIP_RANGE_OUT_OF_BOUNDS 2u
+typedef struct snappy_hip_range {
+	uint64_t offset;      /* first uncompressed byte of the container            */
+	uint64_t length;      /* bytes                                               */
+	void *dst;            /* device: length bytes, any alignment                 */
+	uint32_t stream;      /* index into d_descs                                  */
+	uint32_t pad;
+} snappy_hip_range;
+SNAPPY_HIP_API uint64_t snappy_hip_decompress_ranges_scratch_bytes(uint32_t max_block_size, uint32_t range_count);
+SNAPPY_HIP_API int snappy_hip_decompress_ranges(const snappy_hip_stream_desc *d_descs, uint32_t count, const snappy_hip_range *d_ranges,
+                                 uint32_t range_count, uint32_t *d_status, uint32_t max_block_size, void *d_scratch,
+                                 uint64_t scratch_bytes, void *stream);
+
+/* ---- 1b. drop-in level: one byte range of a framed file ----------------- */
+
+/*
+ * Bytes [offset, offset + length) of the framed stream in input (the whole file: input->buffer at its first byte,
+ * input->length = file size).  Parses the header, walks the u32 size chain on the host only up to the last block the range
+ * touches, copies only those blocks to the device, decodes them there (snappy_hip_decompress_ranges, one range, the
+ * current device) and copies `length` bytes out.  output as in snappy_compress_gpu: realloc'd to `length` bytes, or used as
+ * is when output->max is finite (SNAPPY_BUFFER_TOO_SMALL if length does not fit).  output->length = length on success.
+ * SNAPPY_INVALID_INPUT: a malformed header or chain, offset + length beyond the uncompressed length, or a touched block that
+ * does not decode (the strictness of snappy_decompress_gpu).  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_range_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                          uint64_t offset, uint64_t length, struct program_runtime *runtime);
+
 #ifdef __cplusplus
 }
 #endif

@@ -641,6 +641,145 @@ snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host
     return SNAPPY_OK;
 }
 
+// One byte range of a framed file (snappy_decompress_range_gpu): the header, the size chain on the host up to the last block
+// the range touches, only those blocks' bytes to the device, one range through snappy_hip_decompress_ranges on the current
+// device, `length` bytes back.  Phased and synchronous, as the reference's own steps (snappy_decompress.c:292-493).
+struct DeviceBuffers {
+    std::vector<void*> mem;
+    ~DeviceBuffers()
+    {
+        for (void* p : mem) (void)hipFree(p);
+    }
+    int alloc(void** p, size_t n)
+    {
+        HIP_TRY(hipMalloc(p, n ? n : 1));
+        mem.push_back(*p);
+        return 0;
+    }
+};
+
+snappy_status decompress_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint64_t offset,
+                                        uint64_t length, struct program_runtime* runtime)
+{
+    double t0 = now_seconds();
+    if (!input || !output || !runtime || !input->buffer) return SNAPPY_INVALID_INPUT;
+    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length;
+    uint32_t total = 0, bs = 0;
+    const uint32_t hdr = snappy_hip_parse_header(buf, in_total, &total, &bs);   // snappy_decompress.c:193-198, :298-303
+    if (!hdr) {
+        fprintf(stderr, "Failed to read the stream header\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (offset + length < offset || offset + length > total) {
+        fprintf(stderr, "snappy_hip: range %lu:%lu lies beyond the %u uncompressed bytes\n", (unsigned long)offset, (unsigned long)length, total);
+        return SNAPPY_INVALID_INPUT;
+    }
+    // the output buffer: the caller's (finite max) or ours (snappy_compress_gpu's rule)
+    const bool caller_owned = output->buffer && output->max != ~0UL;
+    if (caller_owned && output->max < length) {
+        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the %lu-byte range\n", (unsigned long)output->max,
+                (unsigned long)length);
+        return SNAPPY_BUFFER_TOO_SMALL;
+    }
+    if (!caller_owned) {
+        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, length ? length : 1);
+        if (!nbuf) {
+            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)length);
+            return SNAPPY_BUFFER_TOO_SMALL;
+        }
+        output->buffer = nbuf;
+    }
+    output->length = 0;
+    output->curr = output->buffer;
+    if (length == 0) {
+        runtime->pre += now_seconds() - t0;
+        return SNAPPY_OK;
+    }
+    if (!block_size_ok(bs)) {
+        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
+        return SNAPPY_INVALID_INPUT;
+    }
+    const uint64_t first = offset / bs, last = (offset + length - 1) / bs;
+    if (last + 1 > (in_total - hdr) / 4) {       // every block needs its u32 size prefix: checked before anything is sized by it
+        fprintf(stderr, "snappy_hip: truncated stream (block %lu)\n", (unsigned long)last);
+        return SNAPPY_INVALID_INPUT;
+    }
+    // the chain up to the last touched block (:317-340); offsets relative to the first touched block's
+    std::vector<uint64_t> off(last + 2, 0);
+    const dropin_plan::Walk w = dropin_plan::walk_chain(buf, in_total, 0, off.data(), {0, hdr}, last + 1);
+    if (w.stop != dropin_plan::kDone) {
+        fprintf(stderr, "snappy_hip: truncated stream (block %lu)\n", (unsigned long)(w.stop == dropin_plan::kLeaves ? w.block + 1 : w.block));
+        return SNAPPY_INVALID_INPUT;
+    }
+    const uint64_t in_lo = off[first], in_len = off[last + 1] - in_lo;
+    for (uint64_t b = 0; b <= last; ++b) off[b] = b >= first ? off[b] - in_lo : 0;
+    if (snappy_hip_device_count() <= 0) {
+        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    const uint64_t pieces = last - first + 1;
+    const uint64_t scratch_bytes = snappy_hip::range_prefix_bytes(1) + std::min<uint64_t>(pieces, range_grid_cap()) * snappy_hip::range_slot_bytes(bs);
+    runtime->pre += now_seconds() - t0;
+
+    DeviceBuffers dev;
+    uint8_t *d_stream = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    uint64_t* d_boff = nullptr;
+    snappy_hip_stream_desc* d_desc = nullptr;
+    snappy_hip_range* d_range = nullptr;
+    uint32_t* d_status = nullptr;
+    double t = now_seconds();
+    if (dev.alloc((void**)&d_stream, in_len) || dev.alloc((void**)&d_boff, (last + 1) * sizeof(uint64_t)) ||
+        dev.alloc((void**)&d_desc, sizeof(snappy_hip_stream_desc)) || dev.alloc((void**)&d_range, sizeof(snappy_hip_range)) ||
+        dev.alloc((void**)&d_status, sizeof(uint32_t)) || dev.alloc((void**)&d_out, length) || dev.alloc((void**)&d_scratch, scratch_bytes))
+        return report("device allocation");
+    runtime->d_alloc = now_seconds() - t;
+    t = now_seconds();
+    if (warm_up_device()) return report("code object load");
+    runtime->load = now_seconds() - t;
+    // copy in: the touched blocks, their offsets and the one descriptor + range
+    snappy_hip_stream_desc desc{d_stream, in_len, d_boff, nullptr, total, bs, hdr, (uint32_t)(last + 1)};
+    snappy_hip_range range{offset, length, d_out, 0, 0};
+    t = now_seconds();
+    if (hipMemcpy(d_stream, buf + in_lo, in_len, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_boff, off.data(), (last + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_desc, &desc, sizeof desc, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_range, &range, sizeof range, hipMemcpyHostToDevice) != hipSuccess) {
+        g_last_error = "hipMemcpy to the device";
+        return report("host-to-device copy");
+    }
+    runtime->copy_in = now_seconds() - t;
+    t = now_seconds();
+    if (snappy_hip_decompress_ranges(d_desc, 1, d_range, 1, d_status, bs, d_scratch, scratch_bytes, nullptr) != SNAPPY_HIP_OK)
+        return report("range decode launch");
+    if (hipDeviceSynchronize() != hipSuccess) {
+        g_last_error = "hipDeviceSynchronize after the range decode";
+        return report("range decode");
+    }
+    runtime->run = now_seconds() - t;
+    t = now_seconds();
+    uint32_t status = 0xffffffffu;
+    if (hipMemcpy(&status, d_status, sizeof status, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(output->buffer, d_out, length, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_last_error = "hipMemcpy to the host";
+        return report("device-to-host copy");
+    }
+    runtime->copy_out = now_seconds() - t;
+    t = now_seconds();
+    for (void* p : dev.mem) (void)hipFree(p);
+    dev.mem.clear();
+    runtime->d_free = now_seconds() - t;
+    if (status != SNAPPY_HIP_BLOCK_OK) {
+        fprintf(stderr, "snappy_hip: a block of the range [%lu, %lu) does not decode (status %u)\n", (unsigned long)offset,
+                (unsigned long)(offset + length), status);
+        return SNAPPY_INVALID_INPUT;
+    }
+    output->length = length;
+    output->curr = output->buffer + length;
+    return SNAPPY_OK;
+}
+
 // The exported pair: one call at a time per process (the cached pipeline streams and their page-locked scratch are per
 // process; the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618), the caller's
 // current HIP device restored on every return path, and no C++ exception crosses the C boundary.
@@ -676,6 +815,12 @@ snappy_status snappy_decompress_gpu(struct host_buffer_context* input, struct ho
                                     struct program_runtime* runtime)
 {
     return entry_guard([&] { return decompress_gpu_body(input, output, runtime); });
+}
+
+snappy_status snappy_decompress_range_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint64_t offset,
+                                          uint64_t length, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return decompress_range_gpu_body(input, output, offset, length, runtime); });
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include "launch_shape.hpp"
 #include "dropin_plan.hpp"
 #include "snappy_kernels.hpp"
+#include "snappy_ranges.hpp"
 
 namespace {
 
@@ -840,6 +841,51 @@ int snappy_hip_decompress_blocks_batch(const struct snappy_hip_decompress_item* 
         if (w.count)
             if (int rc = launch_decompress(w, block_size, stream)) return rc;
     }
+    return SNAPPY_HIP_OK;
+}
+
+// ---- byte ranges (snappy_ranges.hpp) ----
+static uint32_t range_grid_cap()
+{
+    const launch_shape::DeviceShape shape = device_shape();
+    const int cap = std::max(1, env_int("SNAPPY_HIP_K2_WAVES", (int)shape.wave_slots()));
+    return launch_shape::k2_launch_waves(shape, ~0ull, cap);
+}
+
+uint64_t snappy_hip_decompress_ranges_scratch_bytes(uint32_t max_block_size, uint32_t range_count)
+{
+    if (!block_size_ok(max_block_size)) return 0;
+    return snappy_hip::range_prefix_bytes(range_count) + (uint64_t)range_grid_cap() * snappy_hip::range_slot_bytes(max_block_size);
+}
+
+int snappy_hip_decompress_ranges(const snappy_hip_stream_desc* d_descs, uint32_t count, const snappy_hip_range* d_ranges, uint32_t range_count,
+                                 uint32_t* d_status, uint32_t max_block_size, void* d_scratch, uint64_t scratch_bytes, void* stream)
+{
+    static_assert(sizeof(snappy_hip_range) == sizeof(snappy_hip::RangeDesc), "snappy_hip_range layout");
+    static_assert(sizeof(snappy_hip_stream_desc) == sizeof(snappy_hip::StreamDesc), "snappy_hip_stream_desc layout");
+    if (range_count == 0) return SNAPPY_HIP_OK;
+    if (!block_size_ok(max_block_size)) return fail(SNAPPY_HIP_ERR_ARG, "max_block_size must be 1..65535");
+    if (!d_ranges || !d_status || (!d_descs && count)) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    const uint64_t prefix_bytes = snappy_hip::range_prefix_bytes(range_count), slot_bytes = snappy_hip::range_slot_bytes(max_block_size);
+    const uint64_t slots = scratch_bytes > prefix_bytes ? (scratch_bytes - prefix_bytes) / slot_bytes : 0;
+    if (slots == 0) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small for one slot (snappy_hip_decompress_ranges_scratch_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t* prefix = static_cast<uint64_t*>(d_scratch);
+    uint8_t* slot_base = static_cast<uint8_t*>(d_scratch) + prefix_bytes;
+    const auto* descs = reinterpret_cast<const snappy_hip::StreamDesc*>(d_descs);
+    const auto* ranges = reinterpret_cast<const snappy_hip::RangeDesc*>(d_ranges);
+    hipLaunchKernelGGL(snappy_hip::range_pieces_kernel, dim3(1), dim3(1024), 0, st, descs, count, ranges, range_count, d_status, max_block_size,
+                       prefix);
+    HIP_TRY(hipGetLastError());
+    WorkCounter wc;
+    if (int rc = next_work_counter(&wc, st)) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(range_grid_cap(), slots);
+    hipLaunchKernelGGL(snappy_hip::decompress_ranges_kernel, dim3(grid), dim3(64), 0, st, descs, ranges, range_count, d_status, prefix,
+                       slot_base, (uint32_t)slot_bytes, wc.ptr);
+    const hipError_t launched = hipGetLastError();
+    if (int rc = work_counter_launched(wc, st)) return rc;
+    HIP_TRY(launched);
     return SNAPPY_HIP_OK;
 }
 

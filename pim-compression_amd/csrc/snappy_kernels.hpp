@@ -1880,6 +1880,286 @@ constexpr uint32_t kK2StageBytes = 1536;
 #endif
 constexpr uint32_t kK2WalkLevels = SNAPPY_K2_WALK_LEVELS;
 
+// K2's decoder for ONE block, shared by decompress_blocks_kernel and the range kernel (snappy_ranges.hpp): the block whose u32
+// size prefix is at stream + at is decoded into win[0, out_len) -- written in place, back-references read from there, nothing
+// outside it written whatever the stream holds -- with `stage` (kK2StageBytes of LDS) for one window's output.  Returns
+// kBlockOk / kBlockInvalid.  Wave-uniform arguments; every lane of the wavefront calls it.
+__device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint64_t stream_len, uint64_t at, uint8_t* win,
+                                                   uint32_t out_len, lds_bytes_t stage)
+{
+    const uint32_t lane = threadIdx.x;
+    uint32_t st = kBlockOk;
+    uint32_t csz = 0;
+    if (at + 4 > stream_len) {
+        st = kBlockInvalid;
+    } else {
+        csz = uld32(stream + at);                                    // snappy_decompress.c:229-230
+        if (at + 4 + (uint64_t)csz > stream_len) st = kBlockInvalid;
+    }
+    const uint8_t* __restrict__ src = stream + at + 4;
+    const uint64_t avail = (st == kBlockOk) ? stream_len - (at + 4) : 0;
+
+    uint32_t g = 0;             // window base, multiple of 64 (compressed offset)
+    uint32_t cp = 0, op = 0;    // compressed / output cursors
+    uint64_t w0 = 0;
+    WindowLoad next = {0, 64};  // prefetch of the following 64 bytes (W1), shift applied at use
+    WindowLoad next2 = {0, 64}; // batch form: the 64 bytes after those, so that W1 has arrived when a literal runs on into it
+    bool have_window = false;
+    // batch form: a window wholly inside the stream (all but the last windows of a stream's last blocks) is a plain load at a
+    // 32-bit offset from the block's first element; the others take window_issue()'s clamped address and tail shift
+    const uint32_t avail32 = avail > 0xffffff00ull ? 0xffffff00u : (uint32_t)avail;
+    bool next_tail = true, next2_tail = true;
+    auto issue = [&](uint32_t base, bool& tail) -> WindowLoad {
+        WindowLoad r;
+        if (base + 72u <= avail32) {
+            r.raw = ld64(src + (base + lane));
+            r.shift = 0;
+            tail = false;
+        } else {
+            r = window_issue(src, (uint64_t)base + lane, avail);
+            tail = true;
+        }
+        return r;
+    };
+    while (st == kBlockOk && cp < csz) {                             // one iteration per 64-byte window
+        // the window registers rotate at the END of a window (see there); only the first window of a block and the one
+        // after a long literal load afresh: all three requests go out before the first is awaited
+        if (!have_window) {
+            g = cp & ~63u;
+            bool cur_tail;
+            const WindowLoad cur = issue(g, cur_tail);
+            next = issue(g + 64u, next_tail);
+            next2 = issue(g + 128u, next2_tail);
+            w0 = cur_tail ? window_value(cur) : cur.raw;
+            have_window = true;
+        }
+        uint32_t offv = 0;
+        const uint32_t wend = (csz < g + 64) ? csz : g + 64;
+        {
+            // ================= the whole window at once =================
+            const uint32_t wlim = wend - g;
+            uint32_t e_type, e_hdr, e_len, e_consumed;
+            unsigned long long REJ;
+            predecode_window(w0, g + lane, csz, e_type, e_hdr, e_len, offv, e_consumed, REJ);
+            const uint32_t advv = __builtin_amdgcn_inverse_ballot_w64(REJ) ? 64u : e_consumed;
+            uint32_t s = cp - g;
+            unsigned long long E = 0;
+            // The serial walk visits every 2^L-th element (L = kK2WalkLevels): jump[k] = the compressed bytes of this element
+            // and its next 2^k - 1 successors, built by doubling (jump[k] = jump[k-1] + jump[k-1] of the start 2^(k-1)
+            // elements ahead: one ds_bpermute per level; nothing is added for a start beyond the window, so the walk still
+            // ends on the first start at or beyond wlim).  The starts in between are filled in afterwards, level by level:
+            // every lane of E whose 2^k-th successor starts inside the window pushes a 1 to it (ds_permute, the forward
+            // form; lanes of E lie on one chain, so their targets are distinct); the other lanes push to lane 0, which
+            // cannot be anybody's successor.
+            {
+                uint32_t jump[kK2WalkLevels + 1], tgt[kK2WalkLevels + 1];
+                jump[0] = advv;
+                tgt[0] = lane + advv;
+#pragma unroll
+                for (uint32_t k = 1; k <= kK2WalkLevels; ++k) {
+                    const uint32_t a_n = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(tgt[k - 1] << 2), (int)jump[k - 1]);
+                    jump[k] = jump[k - 1] + (tgt[k - 1] < wlim ? a_n : 0u);
+                    tgt[k] = lane + jump[k];
+                }
+                k2_chain_walk(jump[kK2WalkLevels], wlim, s, E);
+#pragma unroll
+                for (uint32_t k = kK2WalkLevels; k-- > 0;) {
+                    const bool pusher = __builtin_amdgcn_inverse_ballot_w64(E) && tgt[k] < wlim;
+                    const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(pusher ? tgt[k] << 2 : 0u), pusher ? 1 : 0);
+                    E |= __ballot(got != 0) & ~1ull;
+                }
+            }
+            if (E & REJ) {                                           // an element predecode rejected
+                st = kBlockInvalid;
+                break;
+            }
+            const uint32_t mylen = __builtin_amdgcn_inverse_ballot_w64(E) ? e_len : 0u;
+            const uint32_t incl = wave_inclusive_scan(mylen, lane);
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint32_t rel = incl - mylen;                       // this lane's element inside the window's output
+            const uint32_t dstp = op + rel;                          // ... and inside the block's
+            const unsigned long long COPY = E & __ballot(e_type != 0);
+            if (op + total > out_len || (COPY & (__ballot(offv == 0) | __ballot(offv > dstp)))) {   // strict, cf. :167-173
+                st = kBlockInvalid;
+                break;
+            }
+            // ================= staged in LDS: the window's output is assembled in k2_stage and flushed once =================
+            // Output bytes [op, op + staged) of this window live in stage[0, staged) until the flush; a back-reference into
+            // them costs an LDS round trip instead of a trip to L2.  Only the part of a last literal that runs on beyond the
+            // 64 window bytes ("spill") bypasses the stage: nothing in this window can refer to it.
+            // (the walk ended right behind the window's last element: a literal there ends at pe = s, and only s > 64 can spill)
+            uint32_t le = 0, ps = 0;
+            const uint32_t pe = s;
+            bool spills = false;
+            if (s > 64u) {
+                le = 63u - (uint32_t)__builtin_clzll(E);
+                if ((uint32_t)__builtin_amdgcn_readlane((int)e_type, (int)le) == 0) {
+                    ps = le + (uint32_t)__builtin_amdgcn_readlane((int)e_hdr, (int)le);
+                    spills = true;
+                }
+            }
+            const uint32_t staged = total - (spills ? pe - (ps > 64u ? ps : 64u) : 0u);   // a tag in the last lanes: payload from ps > 64
+            if (staged > kK2StageBytes) {                            // cannot happen: 22 copies of 64 bytes are the most 64 bytes can hold
+                st = kBlockInvalid;
+                break;
+            }
+            // ---- copies, first part.  "Steppable": does not overlap its own destination and is at least 4 bytes long, so ONE
+            //      lane can do it in unaligned dword steps.  Far ones (source wholly before this window's output) load from
+            //      global memory, all of them together: the loads of their first 8 bytes (most copies of a text end there)
+            //      go out HERE, so that they travel while the literal bytes are placed.  Offsets beyond a copy's length are
+            //      clamped to its last dword: those steps reload and rewrite that dword (same bytes, same place), so the
+            //      loads and stores need no predicate of their own ----
+            const unsigned long long STEP = COPY & __ballot(e_len >= 4u) & __ballot(offv >= e_len);
+            const unsigned long long FAR = STEP & __ballot(offv >= rel + e_len);
+            const unsigned long long NEAR = STEP & __ballot(offv <= rel);
+            const bool is_far = __builtin_amdgcn_inverse_ballot_w64(FAR);
+            const uint32_t last = e_len - 4u;
+            const uint32_t far_o1 = 4u < last ? 4u : last;
+            const uint8_t* sbase = win;                              // uniform base + 32-bit lane offset: no 64-bit address arithmetic
+            const uint32_t so = dstp - offv;
+            uint32_t far_v0 = 0, far_v1 = 0;
+            if (is_far) {
+                far_v0 = ld32(sbase + so);
+                far_v1 = ld32(sbase + (so + far_o1));
+            }
+            __builtin_amdgcn_sched_barrier(0);                       // keep the two loads up here
+            // ---- literals: a payload byte belongs to the last element that starts at or below its lane ----
+            {
+                const unsigned long long below = E & (~0ull >> (63u - lane));         // element starts at or below this lane
+                const bool any = below != 0;
+                const uint32_t em = 63u - (uint32_t)__builtin_clzll(below | 1ull);     // branch-free: 0 when there is none
+                const uint32_t packed = rel | (e_hdr << 16) | (e_type << 20);             // offsets inside a window are < 4096
+                const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(em << 2), (int)packed);
+                const uint32_t pstart = em + ((pk >> 16) & 7u);
+                if (any && ((pk >> 20) & 3u) == 0 && lane >= pstart && lane < wlim) stage[(pk & 0xffffu) + lane - pstart] = (uint8_t)w0;
+            }
+            // the spill: the next 64 bytes come from the prefetch registers, anything beyond straight from memory
+            if (spills) {
+                const uint32_t dbase = (uint32_t)__builtin_amdgcn_readlane((int)dstp, (int)le) - ps;   // byte at g + q goes to dbase + q
+                WindowLoad nx = next;
+                SNAPPY_PIN(nx.shift);                                // first use of the prefetch: wait here, not earlier
+                const uint64_t w1 = next_tail ? window_value(nx) : nx.raw;
+                const uint32_t q = 64u + lane;
+                if (q >= ps && q < pe) win[dbase + q] = (uint8_t)w1;
+                if (pe > 128u) {
+                    const uint8_t* __restrict__ p = src + g + 128u;
+                    uint8_t* d = win + (uint32_t)(dbase + 128u);     // dbase may be "negative" (mod 2^32): add before widening
+                    const uint32_t rest = pe - 128u;
+                    uint32_t i = 4 * lane;
+                    for (; i + 4 <= rest; i += 4 * kWave) st32(d + i, ld32(p + i));
+                    for (; i < rest; ++i) d[i] = p[i];
+                }
+            }
+            // ---- copies, second part.  The far copies land in the stage.  Near ones (source wholly inside the stage) go
+            //      LDS -> LDS in rounds: the first copy still to do, with every other near one whose source ends before that
+            //      copy's destination -- all output below it is complete.  The rest (overlapping, i.e. :174-181 replicating
+            //      the last `off` bytes; shorter than 4; source straddling the start of the stage) go one at a time, a lane
+            //      per byte ----
+            {
+                const uint32_t src_end = rel - offv + e_len;         // meaningful for near copies only
+                unsigned long long rem = COPY & ~FAR;
+                lds_bytes_t dp = stage + rel;
+                if (is_far) {
+                    lds_st32u(dp, far_v0);
+                    lds_st32u(dp + far_o1, far_v1);
+                    for (uint32_t base = 8u; base < e_len; base += 16u) {
+                        const uint32_t o0 = base < last ? base : last, o1 = base + 4u < last ? base + 4u : last,
+                                       o2 = base + 8u < last ? base + 8u : last, o3 = base + 12u < last ? base + 12u : last;
+                        const uint32_t v0 = ld32(sbase + (so + o0)), v1 = ld32(sbase + (so + o1)), v2 = ld32(sbase + (so + o2)),
+                                       v3 = ld32(sbase + (so + o3));
+                        lds_st32u(dp + o0, v0);
+                        lds_st32u(dp + o1, v1);
+                        lds_st32u(dp + o2, v2);
+                        lds_st32u(dp + o3, v3);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                while (rem) {
+                    const uint32_t f = (uint32_t)__builtin_ctzll(rem);
+                    const uint32_t fd = (uint32_t)__builtin_amdgcn_readlane((int)rel, (int)f);
+                    if ((NEAR >> f) & 1ull) {
+                        const unsigned long long ready = rem & NEAR & __ballot(src_end <= fd);
+                        if (__builtin_amdgcn_inverse_ballot_w64(ready)) {
+                            lds_bytes_t sp = stage + (rel - offv);
+                            {
+                                const uint32_t o1 = 4u < last ? 4u : last;
+                                const uint32_t v0 = lds_ld32u(sp), v1 = lds_ld32u(sp + o1);
+                                lds_st32u(dp, v0);
+                                lds_st32u(dp + o1, v1);
+                            }
+                            for (uint32_t base = 8u; base < e_len; base += 16u) {
+                                const uint32_t o0 = base < last ? base : last, o1 = base + 4u < last ? base + 4u : last,
+                                               o2 = base + 8u < last ? base + 8u : last, o3 = base + 12u < last ? base + 12u : last;
+                                const uint32_t v0 = lds_ld32u(sp + o0), v1 = lds_ld32u(sp + o1), v2 = lds_ld32u(sp + o2),
+                                               v3 = lds_ld32u(sp + o3);
+                                lds_st32u(dp + o0, v0);
+                                lds_st32u(dp + o1, v1);
+                                lds_st32u(dp + o2, v2);
+                                lds_st32u(dp + o3, v3);
+                            }
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                        rem &= ~ready;
+                        continue;
+                    }
+                    const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)e_len, (int)f);
+                    const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)offv, (int)f);
+                    uint32_t src_idx = lane;
+                    if (off < len) {                                 // overlap: lane % off (lane < 64, off < 64)
+                        const uint32_t q = (lane * kRecip16[off]) >> 16;
+                        src_idx = lane - q * off;
+                    }
+                    if (lane < len) {
+                        const uint32_t at_stage = fd + src_idx;      // source byte = stage[at_stage - off] when that is inside the stage
+                        const uint8_t v = at_stage >= off ? stage[at_stage - off] : win[op + at_stage - off];
+                        stage[fd + lane] = v;
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    rem &= rem - 1;
+                }
+            }
+            // ---- the next window.  Normally the following 64 bytes: rotate the window registers HERE, before the flush, and
+            //      send the new prefetch into the register that just became free.  (Rotating at the top of the next
+            //      iteration makes the compiler copy a register an outstanding load will write; it then waits at the back
+            //      edge for EVERY outstanding vector memory operation, vmcnt(0), the flush stores included -- a full write
+            //      round trip per window.  Here the two prefetches are a window old, and only stores are in flight at the
+            //      back edge.)  After a literal that ran on beyond the next window the block loads afresh ----
+            const uint32_t flush_at = op;
+            op += total;
+            cp = g + s;
+            if (cp < g + 128u) {
+                SNAPPY_PIN(next.raw);
+                SNAPPY_PIN(next2.raw);
+                w0 = next_tail ? window_value(next) : next.raw;
+                next = next2;
+                next_tail = next2_tail;
+                g += 64;
+                next2 = issue(g + 128u, next2_tail);
+            } else {
+                have_window = false;
+            }
+            // ---- flush: stage[0, staged) -> the block's output at op, a dword per lane (the last one clamped back) ----
+            if (staged >= 4u) {
+                {                                                    // the first 256 bytes: all there is in most windows
+                    const uint32_t i = 4u * lane;
+                    const uint32_t o = i + 4u <= staged ? i : staged - 4u;
+                    if (i < staged) st32(win + flush_at + o, lds_ld32u(stage + o));
+                }
+                for (uint32_t i = 4u * (lane + kWave); i < staged; i += 4u * kWave) {
+                    const uint32_t o = i < staged - 4u ? i : staged - 4u;
+                    st32(win + flush_at + o, lds_ld32u(stage + o));
+                }
+            } else if (lane < staged) {
+                win[flush_at + lane] = stage[lane];
+            }
+            __builtin_amdgcn_wave_barrier();
+            continue;
+        }
+    }
+    if (st == kBlockOk && (op != out_len || cp != csz)) st = kBlockInvalid;
+    return st;
+}
+
 // One K2 launch can serve several streams (their own block offsets, output and status arrays; one block size): the
 // persistent wavefronts draw GLOBAL block numbers and map them to (stream, block), so a batch has one tail instead of one
 // per stream -- the decode-side twin of K1Batch.  Passed by value; the kernel argument segment is read with scalar loads.
@@ -1921,279 +2201,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void decom
         const uint64_t ostart = (uint64_t)b * block_size;
         const uint64_t oleft = total_len - ostart;
         const uint32_t out_len = (oleft < block_size) ? (uint32_t)oleft : block_size;
-        uint8_t* dst = w.out[c] + ostart;
-        uint8_t* win = dst;    // the block's output: written in place, back-references read from there
+        uint8_t* win = w.out[c] + ostart;    // the block's output: written in place, back-references read from there
 
-        uint32_t st = kBlockOk;
-        const uint64_t at = block_offsets[b];
-        uint32_t csz = 0;
-        if (at + 4 > stream_len) {
-            st = kBlockInvalid;
-        } else {
-            csz = uld32(stream + at);                                    // snappy_decompress.c:229-230
-            if (at + 4 + (uint64_t)csz > stream_len) st = kBlockInvalid;
-        }
-        const uint8_t* __restrict__ src = stream + at + 4;
-        const uint64_t avail = (st == kBlockOk) ? stream_len - (at + 4) : 0;
-
-        uint32_t g = 0;             // window base, multiple of 64 (compressed offset)
-        uint32_t cp = 0, op = 0;    // compressed / output cursors
-        uint64_t w0 = 0;
-        WindowLoad next = {0, 64};  // prefetch of the following 64 bytes (W1), shift applied at use
-        WindowLoad next2 = {0, 64}; // batch form: the 64 bytes after those, so that W1 has arrived when a literal runs on into it
-        bool have_window = false;
-        // batch form: a window wholly inside the stream (all but the last windows of a stream's last blocks) is a plain load at a
-        // 32-bit offset from the block's first element; the others take window_issue()'s clamped address and tail shift
-        const uint32_t avail32 = avail > 0xffffff00ull ? 0xffffff00u : (uint32_t)avail;
-        bool next_tail = true, next2_tail = true;
-        auto issue = [&](uint32_t base, bool& tail) -> WindowLoad {
-            WindowLoad r;
-            if (base + 72u <= avail32) {
-                r.raw = ld64(src + (base + lane));
-                r.shift = 0;
-                tail = false;
-            } else {
-                r = window_issue(src, (uint64_t)base + lane, avail);
-                tail = true;
-            }
-            return r;
-        };
-        while (st == kBlockOk && cp < csz) {                             // one iteration per 64-byte window
-            // the window registers rotate at the END of a window (see there); only the first window of a block and the one
-            // after a long literal load afresh: all three requests go out before the first is awaited
-            if (!have_window) {
-                g = cp & ~63u;
-                bool cur_tail;
-                const WindowLoad cur = issue(g, cur_tail);
-                next = issue(g + 64u, next_tail);
-                next2 = issue(g + 128u, next2_tail);
-                w0 = cur_tail ? window_value(cur) : cur.raw;
-                have_window = true;
-            }
-            uint32_t offv = 0;
-            const uint32_t wend = (csz < g + 64) ? csz : g + 64;
-            {
-                // ================= the whole window at once =================
-                const uint32_t wlim = wend - g;
-                uint32_t e_type, e_hdr, e_len, e_consumed;
-                unsigned long long REJ;
-                predecode_window(w0, g + lane, csz, e_type, e_hdr, e_len, offv, e_consumed, REJ);
-                const uint32_t advv = __builtin_amdgcn_inverse_ballot_w64(REJ) ? 64u : e_consumed;
-                uint32_t s = cp - g;
-                unsigned long long E = 0;
-                // The serial walk visits every 2^L-th element (L = kK2WalkLevels): jump[k] = the compressed bytes of this element
-                // and its next 2^k - 1 successors, built by doubling (jump[k] = jump[k-1] + jump[k-1] of the start 2^(k-1)
-                // elements ahead: one ds_bpermute per level; nothing is added for a start beyond the window, so the walk still
-                // ends on the first start at or beyond wlim).  The starts in between are filled in afterwards, level by level:
-                // every lane of E whose 2^k-th successor starts inside the window pushes a 1 to it (ds_permute, the forward
-                // form; lanes of E lie on one chain, so their targets are distinct); the other lanes push to lane 0, which
-                // cannot be anybody's successor.
-                {
-                    uint32_t jump[kK2WalkLevels + 1], tgt[kK2WalkLevels + 1];
-                    jump[0] = advv;
-                    tgt[0] = lane + advv;
-#pragma unroll
-                    for (uint32_t k = 1; k <= kK2WalkLevels; ++k) {
-                        const uint32_t a_n = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(tgt[k - 1] << 2), (int)jump[k - 1]);
-                        jump[k] = jump[k - 1] + (tgt[k - 1] < wlim ? a_n : 0u);
-                        tgt[k] = lane + jump[k];
-                    }
-                    k2_chain_walk(jump[kK2WalkLevels], wlim, s, E);
-#pragma unroll
-                    for (uint32_t k = kK2WalkLevels; k-- > 0;) {
-                        const bool pusher = __builtin_amdgcn_inverse_ballot_w64(E) && tgt[k] < wlim;
-                        const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(pusher ? tgt[k] << 2 : 0u), pusher ? 1 : 0);
-                        E |= __ballot(got != 0) & ~1ull;
-                    }
-                }
-                if (E & REJ) {                                           // an element predecode rejected
-                    st = kBlockInvalid;
-                    break;
-                }
-                const uint32_t mylen = __builtin_amdgcn_inverse_ballot_w64(E) ? e_len : 0u;
-                const uint32_t incl = wave_inclusive_scan(mylen, lane);
-                const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                const uint32_t rel = incl - mylen;                       // this lane's element inside the window's output
-                const uint32_t dstp = op + rel;                          // ... and inside the block's
-                const unsigned long long COPY = E & __ballot(e_type != 0);
-                if (op + total > out_len || (COPY & (__ballot(offv == 0) | __ballot(offv > dstp)))) {   // strict, cf. :167-173
-                    st = kBlockInvalid;
-                    break;
-                }
-                // ================= staged in LDS: the window's output is assembled in k2_stage and flushed once =================
-                // Output bytes [op, op + staged) of this window live in stage[0, staged) until the flush; a back-reference into
-                // them costs an LDS round trip instead of a trip to L2.  Only the part of a last literal that runs on beyond the
-                // 64 window bytes ("spill") bypasses the stage: nothing in this window can refer to it.
-                // (the walk ended right behind the window's last element: a literal there ends at pe = s, and only s > 64 can spill)
-                uint32_t le = 0, ps = 0;
-                const uint32_t pe = s;
-                bool spills = false;
-                if (s > 64u) {
-                    le = 63u - (uint32_t)__builtin_clzll(E);
-                    if ((uint32_t)__builtin_amdgcn_readlane((int)e_type, (int)le) == 0) {
-                        ps = le + (uint32_t)__builtin_amdgcn_readlane((int)e_hdr, (int)le);
-                        spills = true;
-                    }
-                }
-                const uint32_t staged = total - (spills ? pe - (ps > 64u ? ps : 64u) : 0u);   // a tag in the last lanes: payload from ps > 64
-                if (staged > kK2StageBytes) {                            // cannot happen: 22 copies of 64 bytes are the most 64 bytes can hold
-                    st = kBlockInvalid;
-                    break;
-                }
-                // ---- copies, first part.  "Steppable": does not overlap its own destination and is at least 4 bytes long, so ONE
-                //      lane can do it in unaligned dword steps.  Far ones (source wholly before this window's output) load from
-                //      global memory, all of them together: the loads of their first 8 bytes (most copies of a text end there)
-                //      go out HERE, so that they travel while the literal bytes are placed.  Offsets beyond a copy's length are
-                //      clamped to its last dword: those steps reload and rewrite that dword (same bytes, same place), so the
-                //      loads and stores need no predicate of their own ----
-                const unsigned long long STEP = COPY & __ballot(e_len >= 4u) & __ballot(offv >= e_len);
-                const unsigned long long FAR = STEP & __ballot(offv >= rel + e_len);
-                const unsigned long long NEAR = STEP & __ballot(offv <= rel);
-                const bool is_far = __builtin_amdgcn_inverse_ballot_w64(FAR);
-                const uint32_t last = e_len - 4u;
-                const uint32_t far_o1 = 4u < last ? 4u : last;
-                const uint8_t* sbase = win;                              // uniform base + 32-bit lane offset: no 64-bit address arithmetic
-                const uint32_t so = dstp - offv;
-                uint32_t far_v0 = 0, far_v1 = 0;
-                if (is_far) {
-                    far_v0 = ld32(sbase + so);
-                    far_v1 = ld32(sbase + (so + far_o1));
-                }
-                __builtin_amdgcn_sched_barrier(0);                       // keep the two loads up here
-                // ---- literals: a payload byte belongs to the last element that starts at or below its lane ----
-                {
-                    const unsigned long long below = E & (~0ull >> (63u - lane));         // element starts at or below this lane
-                    const bool any = below != 0;
-                    const uint32_t em = 63u - (uint32_t)__builtin_clzll(below | 1ull);     // branch-free: 0 when there is none
-                    const uint32_t packed = rel | (e_hdr << 16) | (e_type << 20);             // offsets inside a window are < 4096
-                    const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(em << 2), (int)packed);
-                    const uint32_t pstart = em + ((pk >> 16) & 7u);
-                    if (any && ((pk >> 20) & 3u) == 0 && lane >= pstart && lane < wlim) stage[(pk & 0xffffu) + lane - pstart] = (uint8_t)w0;
-                }
-                // the spill: the next 64 bytes come from the prefetch registers, anything beyond straight from memory
-                if (spills) {
-                    const uint32_t dbase = (uint32_t)__builtin_amdgcn_readlane((int)dstp, (int)le) - ps;   // byte at g + q goes to dbase + q
-                    WindowLoad nx = next;
-                    SNAPPY_PIN(nx.shift);                                // first use of the prefetch: wait here, not earlier
-                    const uint64_t w1 = next_tail ? window_value(nx) : nx.raw;
-                    const uint32_t q = 64u + lane;
-                    if (q >= ps && q < pe) win[dbase + q] = (uint8_t)w1;
-                    if (pe > 128u) {
-                        const uint8_t* __restrict__ p = src + g + 128u;
-                        uint8_t* d = win + (uint32_t)(dbase + 128u);     // dbase may be "negative" (mod 2^32): add before widening
-                        const uint32_t rest = pe - 128u;
-                        uint32_t i = 4 * lane;
-                        for (; i + 4 <= rest; i += 4 * kWave) st32(d + i, ld32(p + i));
-                        for (; i < rest; ++i) d[i] = p[i];
-                    }
-                }
-                // ---- copies, second part.  The far copies land in the stage.  Near ones (source wholly inside the stage) go
-                //      LDS -> LDS in rounds: the first copy still to do, with every other near one whose source ends before that
-                //      copy's destination -- all output below it is complete.  The rest (overlapping, i.e. :174-181 replicating
-                //      the last `off` bytes; shorter than 4; source straddling the start of the stage) go one at a time, a lane
-                //      per byte ----
-                {
-                    const uint32_t src_end = rel - offv + e_len;         // meaningful for near copies only
-                    unsigned long long rem = COPY & ~FAR;
-                    lds_bytes_t dp = stage + rel;
-                    if (is_far) {
-                        lds_st32u(dp, far_v0);
-                        lds_st32u(dp + far_o1, far_v1);
-                        for (uint32_t base = 8u; base < e_len; base += 16u) {
-                            const uint32_t o0 = base < last ? base : last, o1 = base + 4u < last ? base + 4u : last,
-                                           o2 = base + 8u < last ? base + 8u : last, o3 = base + 12u < last ? base + 12u : last;
-                            const uint32_t v0 = ld32(sbase + (so + o0)), v1 = ld32(sbase + (so + o1)), v2 = ld32(sbase + (so + o2)),
-                                           v3 = ld32(sbase + (so + o3));
-                            lds_st32u(dp + o0, v0);
-                            lds_st32u(dp + o1, v1);
-                            lds_st32u(dp + o2, v2);
-                            lds_st32u(dp + o3, v3);
-                        }
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    while (rem) {
-                        const uint32_t f = (uint32_t)__builtin_ctzll(rem);
-                        const uint32_t fd = (uint32_t)__builtin_amdgcn_readlane((int)rel, (int)f);
-                        if ((NEAR >> f) & 1ull) {
-                            const unsigned long long ready = rem & NEAR & __ballot(src_end <= fd);
-                            if (__builtin_amdgcn_inverse_ballot_w64(ready)) {
-                                lds_bytes_t sp = stage + (rel - offv);
-                                {
-                                    const uint32_t o1 = 4u < last ? 4u : last;
-                                    const uint32_t v0 = lds_ld32u(sp), v1 = lds_ld32u(sp + o1);
-                                    lds_st32u(dp, v0);
-                                    lds_st32u(dp + o1, v1);
-                                }
-                                for (uint32_t base = 8u; base < e_len; base += 16u) {
-                                    const uint32_t o0 = base < last ? base : last, o1 = base + 4u < last ? base + 4u : last,
-                                                   o2 = base + 8u < last ? base + 8u : last, o3 = base + 12u < last ? base + 12u : last;
-                                    const uint32_t v0 = lds_ld32u(sp + o0), v1 = lds_ld32u(sp + o1), v2 = lds_ld32u(sp + o2),
-                                                   v3 = lds_ld32u(sp + o3);
-                                    lds_st32u(dp + o0, v0);
-                                    lds_st32u(dp + o1, v1);
-                                    lds_st32u(dp + o2, v2);
-                                    lds_st32u(dp + o3, v3);
-                                }
-                            }
-                            __builtin_amdgcn_wave_barrier();
-                            rem &= ~ready;
-                            continue;
-                        }
-                        const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)e_len, (int)f);
-                        const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)offv, (int)f);
-                        uint32_t src_idx = lane;
-                        if (off < len) {                                 // overlap: lane % off (lane < 64, off < 64)
-                            const uint32_t q = (lane * kRecip16[off]) >> 16;
-                            src_idx = lane - q * off;
-                        }
-                        if (lane < len) {
-                            const uint32_t at_stage = fd + src_idx;      // source byte = stage[at_stage - off] when that is inside the stage
-                            const uint8_t v = at_stage >= off ? stage[at_stage - off] : win[op + at_stage - off];
-                            stage[fd + lane] = v;
-                        }
-                        __builtin_amdgcn_wave_barrier();
-                        rem &= rem - 1;
-                    }
-                }
-                // ---- the next window.  Normally the following 64 bytes: rotate the window registers HERE, before the flush, and
-                //      send the new prefetch into the register that just became free.  (Rotating at the top of the next
-                //      iteration makes the compiler copy a register an outstanding load will write; it then waits at the back
-                //      edge for EVERY outstanding vector memory operation, vmcnt(0), the flush stores included -- a full write
-                //      round trip per window.  Here the two prefetches are a window old, and only stores are in flight at the
-                //      back edge.)  After a literal that ran on beyond the next window the block loads afresh ----
-                const uint32_t flush_at = op;
-                op += total;
-                cp = g + s;
-                if (cp < g + 128u) {
-                    SNAPPY_PIN(next.raw);
-                    SNAPPY_PIN(next2.raw);
-                    w0 = next_tail ? window_value(next) : next.raw;
-                    next = next2;
-                    next_tail = next2_tail;
-                    g += 64;
-                    next2 = issue(g + 128u, next2_tail);
-                } else {
-                    have_window = false;
-                }
-                // ---- flush: stage[0, staged) -> the block's output at op, a dword per lane (the last one clamped back) ----
-                if (staged >= 4u) {
-                    {                                                    // the first 256 bytes: all there is in most windows
-                        const uint32_t i = 4u * lane;
-                        const uint32_t o = i + 4u <= staged ? i : staged - 4u;
-                        if (i < staged) st32(win + flush_at + o, lds_ld32u(stage + o));
-                    }
-                    for (uint32_t i = 4u * (lane + kWave); i < staged; i += 4u * kWave) {
-                        const uint32_t o = i + 4u <= staged ? i : staged - 4u;
-                        st32(win + flush_at + o, lds_ld32u(stage + o));
-                    }
-                } else if (lane < staged) {
-                    win[flush_at + lane] = stage[lane];
-                }
-                __builtin_amdgcn_wave_barrier();
-                continue;
-            }
-        }
-        if (st == kBlockOk && (op != out_len || cp != csz)) st = kBlockInvalid;
+        const uint32_t st = k2_decode_block(stream, stream_len, block_offsets[b], win, out_len, stage);
 
         if (lane == 0) status[b] = st;
         __syncthreads();

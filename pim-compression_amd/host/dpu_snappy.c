@@ -22,7 +22,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "**DEBUG BUILD**\n");
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
-	fprintf(stderr, "usage: %s [-d] [-c] [-b <block_size>] [-g <gpus>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "usage: %s [-d] [-c] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
@@ -93,8 +93,25 @@ int main(int argc, char **argv)
 	input.max = ULONG_MAX;
 	output.max = ULONG_MAX;
 
-	while ((opt = getopt(argc, argv, "dcb:g:i:o:")) != -1) {
+	int use_range = 0;
+	unsigned long long range_off = 0, range_len = 0;
+	while ((opt = getopt(argc, argv, "dcb:g:i:o:r:")) != -1) {
 		switch (opt) {
+		case 'r': {                  /* decompress only bytes [offset, offset + length) of the container */
+			char *colon = NULL, *tail = NULL;
+			range_off = strtoull(optarg, &colon, 10);
+			if (colon == optarg || *colon != ':' || optarg[0] == '-' || colon[1] == '-' || colon[1] == '\0') {
+				fprintf(stderr, "-r wants <offset>:<length> in bytes, got '%s'\n", optarg);
+				return -2;
+			}
+			range_len = strtoull(colon + 1, &tail, 10);
+			if (*tail != '\0') {
+				fprintf(stderr, "-r wants <offset>:<length> in bytes, got '%s'\n", optarg);
+				return -2;
+			}
+			use_range = 1;
+			break;
+		}
 		case 'd': use_gpu = 1; break;
 		case 'c': compress = 1; break;
 		case 'b': block_size = atoi(optarg); break;
@@ -109,6 +126,10 @@ int main(int argc, char **argv)
 	if (!in_path) {
 		usage(argv[0]);
 		return -1;
+	}
+	if (use_range && compress) {
+		fprintf(stderr, "-r selects a range of a compressed file: it does not go with -c\n");
+		return -2;
 	}
 	if (use_gpu) {
 		/* the overlapped copy-in / kernel / copy-out pipeline of the library keeps six HIP streams busy; HIP maps
@@ -158,6 +179,19 @@ int main(int argc, char **argv)
 		} else {
 			gettimeofday(&t0, NULL);
 			st = snappy_compress_host(&input, &output, (uint32_t)block_size);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+	} else if (use_range) {
+		/* only the blocks the range touches are decoded; the output holds exactly the range's bytes */
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		if (use_gpu) {
+			st = snappy_decompress_range_gpu(&input, &output, range_off, range_len, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = snappy_decompress_range_host(&input, &output, range_off, range_len);
 			gettimeofday(&t1, NULL);
 			rt.run = get_runtime(&t0, &t1);
 		}

@@ -217,6 +217,57 @@ snappy_status setup_decompression(struct host_buffer_context *input, struct host
 	return SNAPPY_OK;
 }
 
+/* The elements of one block (snappy_decompress.c:232-285): ip .. bend decoded to op; back-references may reach down to
+ * out0, output may grow up to out_end.  Returns the new output position, NULL if the block is malformed. */
+static uint8_t *decompress_block_host(const uint8_t *ip, const uint8_t *bend, uint8_t *const out0, uint8_t *op, uint8_t *const out_end)
+{
+	while (ip < bend) {                               /* :232-285 */
+		uint32_t tag = *ip++, len, off;
+		if ((tag & 3) == 0) {
+			len = (tag >> 2) + 1;
+			if (len > 60) {
+				uint32_t nb = len - 60;
+				if ((uint32_t)(bend - ip) < nb)
+					return NULL;
+				len = 0;
+				for (uint32_t k = 0; k < nb; k++)
+					len |= (uint32_t)ip[k] << (8 * k);
+				len += 1;
+				ip += nb;
+			}
+			if (len == 0 || (unsigned long)(bend - ip) < len || (unsigned long)(out_end - op) < len)
+				return NULL;
+			memcpy(op, ip, len);
+			ip += len;
+			op += len;
+			continue;
+		}
+		uint32_t need = (tag & 3) == 1 ? 1 : ((tag & 3) == 2 ? 2 : 4);
+		if ((uint32_t)(bend - ip) < need)
+			return NULL;
+		if ((tag & 3) == 1) {
+			len = ((tag >> 2) & 7) + 4;
+			off = ((tag >> 5) << 8) | ip[0];
+		} else if ((tag & 3) == 2) {
+			len = (tag >> 2) + 1;
+			off = ip[0] | ((uint32_t)ip[1] << 8);
+		} else {
+			len = (tag >> 2) + 1;
+			off = load32(ip);
+		}
+		ip += need;
+		if (off == 0 || (unsigned long)(op - out0) < off) {
+			printf("bad offset!\n");                    /* :171 */
+			return NULL;
+		}
+		if ((unsigned long)(out_end - op) < len)
+			return NULL;
+		for (const uint8_t *from = op - off; len; len--)
+			*op++ = *from++;
+	}
+	return op;
+}
+
 snappy_status snappy_decompress_host(struct host_buffer_context *input, struct host_buffer_context *output)
 {
 	const uint8_t *end = input->buffer + input->length;
@@ -237,52 +288,70 @@ snappy_status snappy_decompress_host(struct host_buffer_context *input, struct h
 		if ((unsigned long)(end - ip) < csz)
 			return SNAPPY_INVALID_INPUT;
 		const uint8_t *bend = ip + csz;
-		while (ip < bend) {                               /* :232-285 */
-			uint32_t tag = *ip++, len, off;
-			if ((tag & 3) == 0) {
-				len = (tag >> 2) + 1;
-				if (len > 60) {
-					uint32_t nb = len - 60;
-					if ((uint32_t)(bend - ip) < nb)
-						return SNAPPY_INVALID_INPUT;
-					len = 0;
-					for (uint32_t k = 0; k < nb; k++)
-						len |= (uint32_t)ip[k] << (8 * k);
-					len += 1;
-					ip += nb;
-				}
-				if (len == 0 || (unsigned long)(bend - ip) < len || (unsigned long)(out_end - op) < len)
-					return SNAPPY_INVALID_INPUT;
-				memcpy(op, ip, len);
-				ip += len;
-				op += len;
-				continue;
-			}
-			uint32_t need = (tag & 3) == 1 ? 1 : ((tag & 3) == 2 ? 2 : 4);
-			if ((uint32_t)(bend - ip) < need)
-				return SNAPPY_INVALID_INPUT;
-			if ((tag & 3) == 1) {
-				len = ((tag >> 2) & 7) + 4;
-				off = ((tag >> 5) << 8) | ip[0];
-			} else if ((tag & 3) == 2) {
-				len = (tag >> 2) + 1;
-				off = ip[0] | ((uint32_t)ip[1] << 8);
-			} else {
-				len = (tag >> 2) + 1;
-				off = load32(ip);
-			}
-			ip += need;
-			if (off == 0 || (unsigned long)(op - out0) < off) {
-				printf("bad offset!\n");                    /* :171 */
-				return SNAPPY_INVALID_INPUT;
-			}
-			if ((unsigned long)(out_end - op) < len)
-				return SNAPPY_INVALID_INPUT;
-			for (const uint8_t *from = op - off; len; len--)
-				*op++ = *from++;
-		}
+		op = decompress_block_host(ip, bend, out0, op, out_end);
+		if (!op)
+			return SNAPPY_INVALID_INPUT;
+		ip = bend;
 	}
 	input->curr = (uint8_t *)ip;
 	output->curr = op;
 	return (op == out_end) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
+}
+
+/* Bytes [offset, offset + length) of a whole framed file (input->buffer at its first byte): the size chain walked up to the
+ * last block the range touches, only the touched blocks decoded.  output->buffer is malloc'd here (length bytes). */
+snappy_status snappy_decompress_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,
+                                           uint64_t length)
+{
+	const uint8_t *const end = input->buffer + input->length;
+	uint32_t total, bs;
+	const uint8_t *ip = varint_get(input->buffer, end, &total);
+	if (ip)
+		ip = varint_get(ip, end, &bs);
+	if (!ip) {
+		fprintf(stderr, "Failed to read the stream header\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (offset + length < offset || offset + length > total) {
+		fprintf(stderr, "range %lu:%lu lies beyond the %u uncompressed bytes\n", (unsigned long)offset, (unsigned long)length, total);
+		return SNAPPY_INVALID_INPUT;
+	}
+	output->buffer = malloc(length ? length : 1);
+	if (!output->buffer)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	output->curr = output->buffer;
+	output->length = length;
+	if (length == 0)
+		return SNAPPY_OK;
+	if (bs == 0)
+		return SNAPPY_INVALID_INPUT;
+	const uint64_t first = offset / bs, last = (offset + length - 1) / bs;
+	const uint64_t lo = first * bs, hi = (last + 1) * (uint64_t)bs < total ? (last + 1) * (uint64_t)bs : total;
+	uint8_t *tmp = malloc(hi - lo);
+	if (!tmp)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	snappy_status st = SNAPPY_OK;
+	for (uint64_t b = 0; b <= last && st == SNAPPY_OK; b++) {       /* the chain (:227-231) up to the last touched block */
+		if (end - ip < 4) {
+			st = SNAPPY_INVALID_INPUT;
+			break;
+		}
+		const uint32_t csz = load32(ip);
+		ip += 4;
+		if ((unsigned long)(end - ip) < csz) {
+			st = SNAPPY_INVALID_INPUT;
+			break;
+		}
+		if (b >= first) {            /* a touched block: exactly its own bytes, at its own place */
+			uint8_t *const bout = tmp + (b * bs - lo);
+			const uint64_t blen = (b + 1) * (uint64_t)bs < total ? bs : total - b * (uint64_t)bs;
+			if (decompress_block_host(ip, ip + csz, bout, bout, bout + blen) != bout + blen)
+				st = SNAPPY_INVALID_INPUT;
+		}
+		ip += csz;
+	}
+	if (st == SNAPPY_OK)
+		memcpy(output->buffer, tmp + (offset - lo), length);
+	free(tmp);
+	return st;
 }

@@ -17,6 +17,9 @@ void setup_compression(struct host_buffer_context *input, struct host_buffer_con
 snappy_status snappy_compress_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t block_size);
 snappy_status setup_decompression(struct host_buffer_context *input, struct host_buffer_context *output, struct program_runtime *runtime);
 snappy_status snappy_decompress_host(struct host_buffer_context *input, struct host_buffer_context *output);
+/* dpu_snappy -r: one byte range of a whole framed file, decoding only the blocks it touches (each on its own) */
+snappy_status snappy_decompress_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,
+                                           uint64_t length);
 double get_runtime(struct timeval *start, struct timeval *end);
 
 #ifdef __cplusplus

@@ -90,6 +90,13 @@ def lib():
         L.snappy_hip_verify_index.argtypes = [vp, u32, vp]
         L.snappy_hip_decompress_blocks.restype = ctypes.c_int
         L.snappy_hip_decompress_blocks.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp]
+        L.snappy_hip_decompress_ranges_scratch_bytes.restype = u64
+        L.snappy_hip_decompress_ranges_scratch_bytes.argtypes = [u32, u32]
+        L.snappy_hip_decompress_ranges.restype = ctypes.c_int
+        L.snappy_hip_decompress_ranges.argtypes = [vp, u32, vp, u32, vp, u32, vp, u64, vp]
+        L.snappy_decompress_range_gpu.restype = ctypes.c_int
+        L.snappy_decompress_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64, u64,
+                                                  ctypes.POINTER(ProgramRuntime)]
         L.snappy_compress_gpu.restype = ctypes.c_int
         L.snappy_compress_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
                                           ctypes.POINTER(ProgramRuntime)]
@@ -311,6 +318,38 @@ def decompress_resident(d_stream, stream_len=None):
     return (1 if bad else 0), d_out[:total]
 
 
+# byte ranges of framed containers (snappy_hip_decompress_ranges)
+RANGE_OUT_OF_BOUNDS = 2
+RANGE_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8"), ("dst", "<u8"), ("stream", "<u4"), ("pad", "<u4")])   # snappy_hip_range
+
+
+def decompress_ranges_scratch_bytes(max_block_size, range_count):
+    """Scratch for a full grid of snappy_hip_decompress_ranges on the current device (0 for a bad max_block_size)."""
+    return int(lib().snappy_hip_decompress_ranges_scratch_bytes(max_block_size, range_count))
+
+
+def make_ranges(entries, device="cuda"):
+    """entries: list of (stream index, offset, length, dst) with dst a device address (int) -> device tensor of snappy_hip_range."""
+    import torch
+    arr = np.zeros(len(entries), dtype=RANGE_DTYPE)
+    for i, (s, off, length, dst) in enumerate(entries):
+        arr[i] = (off, length, dst, s, 0)
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
+def decompress_ranges(d_descs, count, d_ranges, range_count, d_status, max_block_size, d_scratch=None):
+    """Enqueue snappy_hip_decompress_ranges on the current stream.  d_descs: make_stream_descs() tensor (block_offsets filled
+    in), d_ranges: make_ranges() tensor or any device uint8 tensor of packed snappy_hip_range, d_status: device int32 tensor of
+    range_count entries.  d_scratch: 256-byte aligned device uint8 tensor (default: a fresh one for the full grid)."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(decompress_ranges_scratch_bytes(max_block_size, range_count), dtype=torch.uint8, device=d_status.device)
+    _check(lib().snappy_hip_decompress_ranges(d_descs.data_ptr(), count, d_ranges.data_ptr(), range_count, d_status.data_ptr(),
+                                              max_block_size, d_scratch.data_ptr(), d_scratch.numel(), _stream_handle(torch)),
+           "snappy_hip_decompress_ranges")
+    return d_scratch
+
+
 # ---------------------------------------------------------------------------
 # drop-in pair (host buffers), driven the way dpu_snappy.c's main() drives the *_dpu functions
 # ---------------------------------------------------------------------------
@@ -361,3 +400,21 @@ def decompress_host(stream, out_len_override=None):
     plain = ctypes.string_at(out.buffer, total) if st == SNAPPY_OK else b""
     libc().free(buf)
     return st, plain, rt.as_dict()
+
+
+def decompress_range_host(stream, offset, length, out_capacity=None):
+    """snappy_decompress_range_gpu on a whole framed file held in host memory -> (status, bytes, runtime dict).
+    out_capacity: hand over a caller-owned output buffer of that many bytes (finite `max`) instead of letting the callee allocate."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
+    if out_capacity is None:
+        out = HostBufferContext(b"<memory>", None, None, 0, (1 << 64) - 1)
+    else:
+        buf = libc().malloc(max(1, out_capacity))
+        out = HostBufferContext(b"<memory>", buf, buf, 0, out_capacity)
+    rt = ProgramRuntime()
+    st = lib().snappy_decompress_range_gpu(ctypes.byref(inp), ctypes.byref(out), offset, length, ctypes.byref(rt))
+    data = ctypes.string_at(out.buffer, out.length) if st == SNAPPY_OK else b""
+    if out.buffer:
+        libc().free(out.buffer)
+    return st, data, rt.as_dict()
