@@ -297,6 +297,76 @@ SNAPPY_HIP_API int snappy_hip_decompress_ranges(const snappy_hip_stream_desc *d_
                                  uint32_t range_count, uint32_t *d_status, uint32_t max_block_size, void *d_scratch,
                                  uint64_t scratch_bytes, void *stream);
 
+/*
+ * Byte ranges of ONE framed container overwritten, recompressing only the blocks they touch.  Write i puts `length` bytes
+ * from src over uncompressed bytes [offset, offset + length) of the container d_desc describes.  The blocks the writes
+ * touch ("dirty") are decoded (K2's decoder), patched and compressed again (K1, LDS-table form); every other block's
+ * `u32 size + elements` are copied as they are.  Blocks are independent and K1 is bit-identical to the reference per block,
+ * so for a container this library, the reference or any compressor with the reference's per-block output produced,
+ *     the new stream == the compressor's output for the plaintext with the writes applied, byte for byte.
+ * Overwrites only: total_len, block_size and the number of blocks do not change.
+ *
+ * d_desc: device, ONE snappy_hip_stream_desc as snappy_hip_decompress_ranges reads it (stream, stream_len, block_offsets of
+ *   num_blocks entries, total_len, block_size, num_blocks; result is not read).  total_len and block_size are the host's
+ *   copies of its fields: they size the launches.  A descriptor that disagrees with them is REJECTED (below).
+ * d_writes, d_write_status: device arrays of write_count entries.  The writes are SORTED BY OFFSET AND DO NOT OVERLAP: write
+ *   i starts at or after the end of write i - 1 (a block finds its writes by binary search).  Checked on the device.  A write
+ *   of length 0 is allowed and dirties nothing.
+ * d_new_stream (new_stream_capacity bytes): the header, then every block in order.  d_new_offsets (num_blocks + 1 entries,
+ *   as snappy_hip_compact leaves them): [b] = offset of block b's size prefix, [num_blocks] = *d_new_stream_len = the new
+ *   length.  The old stream is never written; d_new_stream must not overlap it, the sources or the scratch.
+ * d_write_status[i] (always written):
+ *   SNAPPY_HIP_BLOCK_OK             the write is well-formed;
+ *   SNAPPY_HIP_RANGE_OUT_OF_BOUNDS  offset + length beyond total_len or overflowing, or a null src with length > 0;
+ *   SNAPPY_HIP_WRITE_UNORDERED      it starts before the end of the write in front of it (the end of an overflowing write
+ *                                   counts as infinite).
+ * d_result[0] (always written), d_result[1] = the number of dirty blocks:
+ *   SNAPPY_HIP_BLOCK_OK             done.
+ *   SNAPPY_HIP_UPDATE_REJECTED      all or nothing: some write is not OK, or the writes dirty more than max_dirty_blocks
+ *                                   blocks (d_result[1] = how many), or the new length exceeds new_stream_capacity, or the
+ *                                   descriptor's total_len / block_size / num_blocks are not the host's.  *d_new_stream_len
+ *                                   = 0 and NOT ONE BYTE of d_new_stream or d_new_offsets is written.  The later kernels read
+ *                                   the verdict from device memory and leave; the host is not asked.
+ *   SNAPPY_HIP_BLOCK_INVALID        the container itself is bad: a clean block whose chain link does not hold
+ *                                   (offsets[b] + 4 + le32(stream + offsets[b]) == offsets[b + 1], the last one against
+ *                                   stream_len: the rule of snappy_hip_verify_index, so a copy never reads outside the
+ *                                   stream), or a dirty block that is only partly overwritten and does not decode under
+ *                                   the strictness of snappy_hip_decompress_blocks.  *d_new_stream_len = 0; the contents of
+ *                                   d_new_stream / d_new_offsets are unspecified; the old stream is intact.
+ *   A dirty block that the writes cover completely (one write or several adjacent ones) is not decoded at all: its old bytes
+ *   cannot matter.  A clean block is copied, NOT decoded: damage inside its payload with an intact link travels along
+ *   into the new stream (snappy_hip_decompress_blocks of the new stream reports it, as it would for the old one).
+ * No write at all gives a copy of the stream (chain checked); total_len == 0 gives the header.
+ *
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_update_scratch_bytes(...) bytes for the same
+ * block_size, number of blocks and max_dirty_blocks on the current device, not shared with a launch that runs
+ * concurrently; contents need not be initialised.  It holds two u32 per block, two u32 and one compressed slot
+ * (snappy_hip_slot_stride) per dirty block, and one patch slot (block_size + 64 bytes, rounded up to 256) per wavefront of
+ * the recompress kernel: min(max_dirty_blocks, the wavefronts resident on the device with K2's stage and the LDS-table
+ * kernel's table in LDS -- four per CU at 32 KiB blocks).
+ * The call only enqueues work on `stream`; it never synchronises and never calls the allocator.  A second update can run on
+ * the first one's outputs: d_new_stream / d_new_offsets go into the next descriptor, with an 8-byte device copy of
+ * *d_new_stream_len into its stream_len.
+ * SNAPPY_HIP_ERR_ARG (host side): null pointers, a bad block size, a scratch that is too small or misaligned,
+ * max_dirty_blocks == 0 with writes present.
+ * Rewriting beats a full recompress only while few blocks are dirty; DESIGN.md 3.5 has the measured crossover.
+ */
+#define SNAPPY_HIP_WRITE_UNORDERED 3u
+#define SNAPPY_HIP_UPDATE_REJECTED 4u
+typedef struct snappy_hip_write {
+	uint64_t offset;      /* first uncompressed byte of the container that is overwritten */
+	uint64_t length;      /* bytes                                               */
+	const void *src;      /* device: length bytes, any alignment                 */
+	uint64_t pad;
+} snappy_hip_write;
+SNAPPY_HIP_API uint64_t snappy_hip_update_scratch_bytes(uint32_t block_size, uint32_t num_blocks, uint32_t write_count,
+                                         uint32_t max_dirty_blocks);
+SNAPPY_HIP_API int snappy_hip_update_ranges(const snappy_hip_stream_desc *d_desc, uint32_t total_len, uint32_t block_size,
+                             const snappy_hip_write *d_writes, uint32_t write_count, uint32_t *d_write_status,
+                             uint8_t *d_new_stream, uint64_t new_stream_capacity, uint64_t *d_new_offsets,
+                             uint64_t *d_new_stream_len, uint32_t *d_result, uint32_t max_dirty_blocks, void *d_scratch,
+                             uint64_t scratch_bytes, void *stream);
+
 /* ---- 1b. drop-in level: one byte range of a framed file ----------------- */
 
 /*
@@ -310,6 +380,18 @@ SNAPPY_HIP_API int snappy_hip_decompress_ranges(const snappy_hip_stream_desc *d_
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_range_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                           uint64_t offset, uint64_t length, struct program_runtime *runtime);
+
+/*
+ * The framed stream in input with bytes [offset, offset + patch->length) of its plaintext replaced by patch->buffer, written
+ * to output (as in snappy_compress_gpu: realloc'd to the new size, or used as is when output->max is finite,
+ * SNAPPY_BUFFER_TOO_SMALL if the new stream does not fit).  Parses the header and walks the whole u32 size chain on the
+ * host, copies the whole stream to the current device, runs one snappy_hip_update_ranges there (only the touched blocks
+ * are decoded and compressed again) and copies the new stream back.  The result is byte for byte what snappy_compress_gpu
+ * gives for the patched plaintext.  SNAPPY_INVALID_INPUT: a malformed header or chain, offset + patch->length beyond the
+ * uncompressed length, or a touched, partly overwritten block that does not decode.  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_update_range_gpu(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
+                                      struct host_buffer_context *output, struct program_runtime *runtime);
 
 #ifdef __cplusplus
 }

@@ -780,6 +780,136 @@ snappy_status decompress_range_gpu_body(struct host_buffer_context* input, struc
     return SNAPPY_OK;
 }
 
+// One overwrite of a framed file (snappy_update_range_gpu): the header and the whole size chain on the host, the whole stream
+// to the current device, one write through snappy_hip_update_ranges, the new stream back.  Phased and synchronous.
+snappy_status update_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* patch, uint64_t offset,
+                                    struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    double t0 = now_seconds();
+    if (!input || !patch || !output || !runtime || !input->buffer || (patch->length && !patch->buffer)) return SNAPPY_INVALID_INPUT;
+    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length, length = patch->length;
+    uint32_t total = 0, bs = 0;
+    const uint32_t hdr = snappy_hip_parse_header(buf, in_total, &total, &bs);
+    if (!hdr) {
+        fprintf(stderr, "Failed to read the stream header\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (offset + length < offset || offset + length > total) {
+        fprintf(stderr, "snappy_hip: write %lu:%lu lies beyond the %u uncompressed bytes\n", (unsigned long)offset, (unsigned long)length, total);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (total && !block_size_ok(bs)) {
+        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
+        return SNAPPY_INVALID_INPUT;
+    }
+    const uint64_t nb = total ? snappy_hip_num_blocks(total, bs) : 0;
+    if (nb > (in_total - hdr) / 4) {             // every block needs its u32 size prefix: checked before anything is sized by it
+        fprintf(stderr, "snappy_hip: truncated stream (%lu blocks)\n", (unsigned long)nb);
+        return SNAPPY_INVALID_INPUT;
+    }
+    std::vector<uint64_t> off(nb + 1, hdr);
+    if (nb) {
+        const dropin_plan::Walk w = dropin_plan::walk_chain(buf, in_total, 0, off.data(), {0, hdr}, nb);
+        if (w.stop != dropin_plan::kDone) {
+            fprintf(stderr, "snappy_hip: truncated stream (block %lu)\n", (unsigned long)(w.stop == dropin_plan::kLeaves ? w.block + 1 : w.block));
+            return SNAPPY_INVALID_INPUT;
+        }
+    }
+    if (off[nb] != in_total) {
+        fprintf(stderr, "snappy_hip: %lu bytes behind the last block\n", (unsigned long)(in_total - off[nb]));
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (snappy_hip_device_count() <= 0) {
+        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    const uint32_t dirty_max = length ? (uint32_t)((offset + length - 1) / bs - offset / bs + 1) : 0;
+    const uint32_t bs_arg = total ? bs : 32768u;          // (an empty container's block size may be anything: nothing is sized by it)
+    // a dirty block grows to a slot at most, a clean one keeps its size
+    const uint64_t capacity = in_total + (uint64_t)dirty_max * snappy_hip_slot_stride(bs_arg) + 16;
+    const uint64_t scratch_bytes = snappy_hip_update_scratch_bytes(bs_arg, (uint32_t)nb, 1, std::max(1u, dirty_max));
+    runtime->pre += now_seconds() - t0;
+
+    DeviceBuffers dev;
+    uint8_t *d_stream = nullptr, *d_new = nullptr, *d_scratch = nullptr, *d_patch = nullptr;
+    uint64_t *d_boff = nullptr, *d_noff = nullptr;      // d_noff: the new offsets, then the new length
+    snappy_hip_stream_desc* d_desc = nullptr;
+    snappy_hip_write* d_write = nullptr;
+    uint32_t* d_words = nullptr;                        // [0] the write's status, [1..2] the result
+    double t = now_seconds();
+    if (dev.alloc((void**)&d_stream, in_total) || dev.alloc((void**)&d_boff, (nb + 1) * sizeof(uint64_t)) ||
+        dev.alloc((void**)&d_noff, (nb + 2) * sizeof(uint64_t)) || dev.alloc((void**)&d_desc, sizeof(snappy_hip_stream_desc)) ||
+        dev.alloc((void**)&d_write, sizeof(snappy_hip_write)) || dev.alloc((void**)&d_words, 4 * sizeof(uint32_t)) ||
+        dev.alloc((void**)&d_patch, length) || dev.alloc((void**)&d_new, capacity) || dev.alloc((void**)&d_scratch, scratch_bytes))
+        return report("device allocation");
+    runtime->d_alloc = now_seconds() - t;
+    t = now_seconds();
+    if (warm_up_device()) return report("code object load");
+    runtime->load = now_seconds() - t;
+    snappy_hip_stream_desc desc{d_stream, in_total, d_boff, nullptr, total, bs_arg, hdr, (uint32_t)nb};
+    snappy_hip_write write{offset, length, d_patch, 0};
+    t = now_seconds();
+    if (hipMemcpy(d_stream, buf, in_total, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_boff, off.data(), (nb + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_desc, &desc, sizeof desc, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_write, &write, sizeof write, hipMemcpyHostToDevice) != hipSuccess ||
+        (length && hipMemcpy(d_patch, patch->buffer, length, hipMemcpyHostToDevice) != hipSuccess)) {
+        g_last_error = "hipMemcpy to the device";
+        return report("host-to-device copy");
+    }
+    runtime->copy_in = now_seconds() - t;
+    t = now_seconds();
+    if (snappy_hip_update_ranges(d_desc, total, bs_arg, d_write, 1, d_words, d_new, capacity, d_noff, d_noff + nb + 1, d_words + 1,
+                                 std::max(1u, dirty_max), d_scratch, scratch_bytes, nullptr) != SNAPPY_HIP_OK)
+        return report("update launch");
+    if (hipDeviceSynchronize() != hipSuccess) {
+        g_last_error = "hipDeviceSynchronize after the update";
+        return report("update");
+    }
+    runtime->run = now_seconds() - t;
+    t = now_seconds();
+    uint32_t words[3] = {0xffffffffu, 0xffffffffu, 0};
+    uint64_t new_len = 0;
+    if (hipMemcpy(words, d_words, sizeof words, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&new_len, d_noff + nb + 1, sizeof new_len, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_last_error = "hipMemcpy to the host";
+        return report("device-to-host copy");
+    }
+    if (words[0] != SNAPPY_HIP_BLOCK_OK || words[1] != SNAPPY_HIP_BLOCK_OK || new_len > capacity) {
+        fprintf(stderr, "snappy_hip: the stream cannot be updated (write status %u, result %u)\n", words[0], words[1]);
+        return SNAPPY_INVALID_INPUT;
+    }
+    // the output buffer: the caller's (finite max) or ours (snappy_compress_gpu's rule)
+    const bool caller_owned = output->buffer && output->max != ~0UL;
+    if (caller_owned && output->max < new_len) {
+        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the %lu-byte stream\n", (unsigned long)output->max,
+                (unsigned long)new_len);
+        return SNAPPY_BUFFER_TOO_SMALL;
+    }
+    if (!caller_owned) {
+        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, new_len ? new_len : 1);
+        if (!nbuf) {
+            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)new_len);
+            return SNAPPY_BUFFER_TOO_SMALL;
+        }
+        output->buffer = nbuf;
+    }
+    if (hipMemcpy(output->buffer, d_new, new_len, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_last_error = "hipMemcpy to the host";
+        return report("device-to-host copy");
+    }
+    runtime->copy_out = now_seconds() - t;
+    t = now_seconds();
+    for (void* p : dev.mem) (void)hipFree(p);
+    dev.mem.clear();
+    runtime->d_free = now_seconds() - t;
+    output->length = new_len;
+    output->curr = output->buffer + new_len;
+    return SNAPPY_OK;
+}
+
 // The exported pair: one call at a time per process (the cached pipeline streams and their page-locked scratch are per
 // process; the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618), the caller's
 // current HIP device restored on every return path, and no C++ exception crosses the C boundary.
@@ -821,6 +951,12 @@ snappy_status snappy_decompress_range_gpu(struct host_buffer_context* input, str
                                           uint64_t length, struct program_runtime* runtime)
 {
     return entry_guard([&] { return decompress_range_gpu_body(input, output, offset, length, runtime); });
+}
+
+snappy_status snappy_update_range_gpu(struct host_buffer_context* input, struct host_buffer_context* patch, uint64_t offset,
+                                      struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return update_range_gpu_body(input, patch, offset, output, runtime); });
 }
 
 }  // extern "C"

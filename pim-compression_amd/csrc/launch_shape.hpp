@@ -103,4 +103,12 @@ inline uint32_t k2_launch_waves(const DeviceShape& d, uint64_t num_blocks, int c
     return (uint32_t)std::min<uint64_t>(std::min<uint64_t>(num_blocks, cap), resident);
 }
 
+// The update's recompress kernel (snappy_update.hpp): resident wavefronts of wave_lds_bytes of LDS each (K2's stage + the
+// LDS-table kernel's table and scratch) -- four per CU at 32 KiB blocks on an MI355X
+inline uint32_t update_resident_waves(const DeviceShape& d, uint32_t wave_lds_bytes)
+{
+    const uint32_t per_cu = std::min<uint32_t>(d.wave_slots_per_cu, d.lds_per_cu / std::max(1u, lds_alloc_bytes(wave_lds_bytes)));
+    return std::max(1u, per_cu) * d.cus;
+}
+
 }  // namespace launch_shape

@@ -26,6 +26,7 @@
 #include "dropin_plan.hpp"
 #include "snappy_kernels.hpp"
 #include "snappy_ranges.hpp"
+#include "snappy_update.hpp"
 
 namespace {
 
@@ -886,6 +887,78 @@ int snappy_hip_decompress_ranges(const snappy_hip_stream_desc* d_descs, uint32_t
     const hipError_t launched = hipGetLastError();
     if (int rc = work_counter_launched(wc, st)) return rc;
     HIP_TRY(launched);
+    return SNAPPY_HIP_OK;
+}
+
+// ---- overwriting byte ranges (snappy_update.hpp) ----
+// dynamic LDS and wavefronts of the recompress kernel: the LDS-table kernel's form and LDS at this block size, plus K2's stage
+static uint32_t update_grid_cap(uint32_t block_size)
+{
+    return launch_shape::update_resident_waves(device_shape(), snappy_hip::kK2StageBytes + lds_table_wave_bytes(block_size));
+}
+
+uint64_t snappy_hip_update_scratch_bytes(uint32_t block_size, uint32_t num_blocks, uint32_t write_count, uint32_t max_dirty_blocks)
+{
+    (void)write_count;      // (the writes are searched where they are; no scratch per write)
+    if (!block_size_ok(block_size)) return 0;
+    const uint32_t waves = std::max(1u, std::min(update_grid_cap(block_size), max_dirty_blocks));
+    return snappy_hip::update_layout(block_size, num_blocks, max_dirty_blocks, waves, snappy_hip_slot_stride(block_size)).total;
+}
+
+int snappy_hip_update_ranges(const snappy_hip_stream_desc* d_desc, uint32_t total_len, uint32_t block_size, const snappy_hip_write* d_writes,
+                             uint32_t write_count, uint32_t* d_write_status, uint8_t* d_new_stream, uint64_t new_stream_capacity,
+                             uint64_t* d_new_offsets, uint64_t* d_new_stream_len, uint32_t* d_result, uint32_t max_dirty_blocks,
+                             void* d_scratch, uint64_t scratch_bytes, void* stream)
+{
+    static_assert(sizeof(snappy_hip_write) == sizeof(snappy_hip::WriteDesc), "snappy_hip_write layout");
+    if (!block_size_ok(block_size)) return fail(SNAPPY_HIP_ERR_ARG, "block_size must be 1..65535");
+    if (!d_desc || !d_new_stream || !d_new_offsets || !d_new_stream_len || !d_result || (write_count && (!d_writes || !d_write_status)))
+        return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (write_count && max_dirty_blocks == 0) return fail(SNAPPY_HIP_ERR_ARG, "max_dirty_blocks must not be 0 when there are writes");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    const uint32_t nb = (uint32_t)snappy_hip_num_blocks(total_len, block_size);
+    const uint32_t stride = snappy_hip_slot_stride(block_size);
+    const uint32_t waves = std::max(1u, std::min(update_grid_cap(block_size), max_dirty_blocks));
+    const snappy_hip::UpdateLayout l = snappy_hip::update_layout(block_size, nb, max_dirty_blocks, waves, stride);
+    if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_update_scratch_bytes)");
+    if (int rc = check_knobs()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
+    uint32_t* span = reinterpret_cast<uint32_t*>(scratch + l.span);
+    uint32_t* rank = reinterpret_cast<uint32_t*>(scratch + l.rank);
+    uint32_t* dirty = reinterpret_cast<uint32_t*>(scratch + l.dirty);
+    uint32_t* dirty_bytes = reinterpret_cast<uint32_t*>(scratch + l.dirty_bytes);
+    const auto* desc = reinterpret_cast<const snappy_hip::StreamDesc*>(d_desc);
+    const auto* writes = reinterpret_cast<const snappy_hip::WriteDesc*>(d_writes);
+    HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
+    if (nb)
+        hipLaunchKernelGGL(snappy_hip::update_mark_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, desc, total_len, block_size, nb, writes,
+                           write_count, ctl, span);
+    hipLaunchKernelGGL(snappy_hip::update_plan_kernel, dim3(1), dim3(1024), 0, st, desc, total_len, block_size, nb, writes, write_count,
+                       d_write_status, max_dirty_blocks, ctl, span, rank, dirty, d_new_stream_len, d_result);
+    HIP_TRY(hipGetLastError());
+    if (write_count && nb) {
+        WorkCounter wc;
+        if (int rc = next_work_counter(&wc, st)) return rc;
+        if (k1_stream_forms(block_size) & 1)
+            hipLaunchKernelGGL(snappy_hip::recompress_dirty_kernel<3>, dim3(waves), dim3(64), snappy_hip::lds_table_stream_lds_bytes(block_size), st,
+                               desc, total_len, block_size, writes, write_count, ctl, dirty, dirty_bytes, scratch + l.patch, l.patch_slot_bytes,
+                               scratch + l.cslots, stride, wc.ptr);
+        else
+            hipLaunchKernelGGL(snappy_hip::recompress_dirty_kernel<2>, dim3(waves), dim3(64), snappy_hip::lds_table_kernel_lds_bytes(block_size, true),
+                               st, desc, total_len, block_size, writes, write_count, ctl, dirty, dirty_bytes, scratch + l.patch,
+                               l.patch_slot_bytes, scratch + l.cslots, stride, wc.ptr);
+        const hipError_t launched = hipGetLastError();
+        if (int rc = work_counter_launched(wc, st)) return rc;
+        HIP_TRY(launched);
+    }
+    hipLaunchKernelGGL(snappy_hip::update_sizes_kernel, dim3(1), dim3(1024), 0, st, total_len, block_size, nb, ctl, span, rank, dirty_bytes,
+                       d_new_stream, new_stream_capacity, d_new_offsets, d_new_stream_len, d_result);
+    if (nb)
+        hipLaunchKernelGGL(snappy_hip::merge_stream_kernel, dim3(nb), dim3(256), 0, st, desc, nb, ctl, rank, scratch + l.cslots, stride,
+                           d_new_offsets, d_new_stream);
+    HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
 }
 

@@ -5,7 +5,7 @@
  * snappy_decompress_dpu (dpu_snappy.c:169-172, :189-192).  Without -d the host CPU codec runs,
  * as in the reference.  -d never falls back to the CPU.
  *
- *   dpu_snappy [-d] [-c] [-b <block_size>] [-g <gpus>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] [-c] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]
  */
 #include <getopt.h>
 #include <limits.h>
@@ -22,11 +22,13 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "**DEBUG BUILD**\n");
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
-	fprintf(stderr, "usage: %s [-d] [-c] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "usage: %s [-d] [-c] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
+	fprintf(stderr, "r: decompress only <length> bytes from uncompressed byte <offset> of the input\n");
+	fprintf(stderr, "w: overwrite the uncompressed bytes from <offset> with <patch_file>, recompressing only the touched blocks\n");
 	fprintf(stderr, "i: input file\n");
 	fprintf(stderr, "o: output file\n");
 }
@@ -95,8 +97,22 @@ int main(int argc, char **argv)
 
 	int use_range = 0;
 	unsigned long long range_off = 0, range_len = 0;
-	while ((opt = getopt(argc, argv, "dcb:g:i:o:r:")) != -1) {
+	int use_write = 0;
+	unsigned long long write_off = 0;
+	const char *patch_path = NULL;
+	while ((opt = getopt(argc, argv, "dcb:g:i:o:r:w:")) != -1) {
 		switch (opt) {
+		case 'w': {                  /* overwrite the uncompressed bytes from offset with the patch file's */
+			char *colon = NULL;
+			write_off = strtoull(optarg, &colon, 10);
+			if (colon == optarg || *colon != ':' || optarg[0] == '-' || colon[1] == '\0') {
+				fprintf(stderr, "-w wants <offset>:<patch_file>, got '%s'\n", optarg);
+				return -2;
+			}
+			patch_path = colon + 1;
+			use_write = 1;
+			break;
+		}
 		case 'r': {                  /* decompress only bytes [offset, offset + length) of the container */
 			char *colon = NULL, *tail = NULL;
 			range_off = strtoull(optarg, &colon, 10);
@@ -129,6 +145,10 @@ int main(int argc, char **argv)
 	}
 	if (use_range && compress) {
 		fprintf(stderr, "-r selects a range of a compressed file: it does not go with -c\n");
+		return -2;
+	}
+	if (use_write && (compress || use_range)) {
+		fprintf(stderr, "-w overwrites bytes of a compressed file: it does not go with -c or -r\n");
 		return -2;
 	}
 	if (use_gpu) {
@@ -182,6 +202,24 @@ int main(int argc, char **argv)
 			gettimeofday(&t1, NULL);
 			rt.run = get_runtime(&t0, &t1);
 		}
+	} else if (use_write) {
+		/* only the blocks the patch touches are decoded and compressed again; the output is the new stream */
+		struct host_buffer_context patch = { 0 };
+		patch.max = ULONG_MAX;
+		patch.file_name = patch_path;
+		if (slurp(patch_path, &patch))
+			return -1;
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		if (use_gpu) {
+			st = snappy_update_range_gpu(&input, &patch, write_off, &output, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = snappy_update_range_host(&input, &patch, write_off, &output);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
 	} else if (use_range) {
 		/* only the blocks the range touches are decoded; the output holds exactly the range's bytes */
 		output.buffer = NULL;
@@ -222,7 +260,7 @@ int main(int argc, char **argv)
 	if (spill(out_path, &output))
 		return -1;
 
-	if (compress) {
+	if (compress || use_write) {          /* (-w: the new stream against the old one) */
 		printf("Compressed %ld bytes to: %s\n", output.length, out_path);
 		printf("Compression ratio: %f\n", 1 - (double)output.length / (double)input.length);
 	} else {

@@ -355,3 +355,76 @@ snappy_status snappy_decompress_range_host(struct host_buffer_context *input, st
 	free(tmp);
 	return st;
 }
+
+/* dpu_snappy -w: `patch` over plaintext bytes [offset, offset + patch->length) of a whole framed file.  The chain is walked
+ * once; a block the patch touches is decoded (unless the patch covers it completely), patched and compressed again, every
+ * other block's size prefix and elements are copied.  output->buffer is malloc'd here. */
+snappy_status snappy_update_range_host(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
+                                       struct host_buffer_context *output)
+{
+	const uint8_t *const end = input->buffer + input->length;
+	const uint64_t length = patch->length;
+	uint32_t total, bs;
+	const uint8_t *ip = varint_get(input->buffer, end, &total);
+	if (ip)
+		ip = varint_get(ip, end, &bs);
+	if (!ip) {
+		fprintf(stderr, "Failed to read the stream header\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (offset + length < offset || offset + length > total) {
+		fprintf(stderr, "write %lu:%lu lies beyond the %u uncompressed bytes\n", (unsigned long)offset, (unsigned long)length, total);
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (total && (bs == 0 || bs > 65535))
+		return SNAPPY_INVALID_INPUT;
+	const uint64_t nb = total ? ((uint64_t)total + bs - 1) / bs : 0;
+	const uint64_t first = length ? offset / bs : 1, last = length ? (offset + length - 1) / bs : 0;   /* first > last: no dirty block */
+	const uint64_t dirty = length ? last - first + 1 : 0;
+	const unsigned long cap = input->length + dirty * (4ul + 32 + bs + bs / 6) + 16;
+	uint8_t *out = malloc(cap), *tmp = malloc((unsigned long)bs + 16);
+	uint16_t *tab = malloc(TABLE_MAX * sizeof(*tab));
+	snappy_status st = (out && tmp && tab) ? SNAPPY_OK : SNAPPY_BUFFER_TOO_SMALL;
+	struct sink s = { out };
+	if (st == SNAPPY_OK) {
+		memcpy(out, input->buffer, (size_t)(ip - input->buffer));      /* the header stays */
+		s.p = out + (ip - input->buffer);
+	}
+	for (uint64_t b = 0; b < nb && st == SNAPPY_OK; b++) {
+		if (end - ip < 4) {
+			st = SNAPPY_INVALID_INPUT;
+			break;
+		}
+		const uint32_t csz = load32(ip);
+		if ((unsigned long)(end - ip - 4) < csz) {
+			st = SNAPPY_INVALID_INPUT;
+			break;
+		}
+		if (b < first || b > last) {
+			memcpy(s.p, ip, 4ul + csz);
+			s.p += 4ul + csz;
+		} else {
+			const uint64_t begin = b * bs, blen = begin + bs < total ? bs : total - begin;
+			const uint64_t from = offset > begin ? offset : begin, to = offset + length < begin + blen ? offset + length : begin + blen;
+			if (to - from < blen && decompress_block_host(ip + 4, ip + 4 + csz, tmp, tmp, tmp + blen) != tmp + blen) {
+				st = SNAPPY_INVALID_INPUT;
+				break;
+			}
+			memcpy(tmp + (from - begin), patch->buffer + (from - offset), to - from);
+			host_compress_block(tmp, (uint32_t)blen, &s, tab);
+		}
+		ip += 4ul + csz;
+	}
+	if (st == SNAPPY_OK && ip != end)
+		st = SNAPPY_INVALID_INPUT;                             /* bytes behind the last block */
+	free(tmp);
+	free(tab);
+	if (st != SNAPPY_OK) {
+		free(out);
+		return st;
+	}
+	output->buffer = out;
+	output->curr = s.p;
+	output->length = (unsigned long)(s.p - out);
+	return SNAPPY_OK;
+}

@@ -20,6 +20,9 @@ snappy_status snappy_decompress_host(struct host_buffer_context *input, struct h
 /* dpu_snappy -r: one byte range of a whole framed file, decoding only the blocks it touches (each on its own) */
 snappy_status snappy_decompress_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,
                                            uint64_t length);
+/* dpu_snappy -w: patch over plaintext bytes [offset, offset + patch->length), recompressing only the blocks it touches */
+snappy_status snappy_update_range_host(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
+                                       struct host_buffer_context *output);
 double get_runtime(struct timeval *start, struct timeval *end);
 
 #ifdef __cplusplus

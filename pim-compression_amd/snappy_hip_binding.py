@@ -97,6 +97,13 @@ def lib():
         L.snappy_decompress_range_gpu.restype = ctypes.c_int
         L.snappy_decompress_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64, u64,
                                                   ctypes.POINTER(ProgramRuntime)]
+        L.snappy_hip_update_scratch_bytes.restype = u64
+        L.snappy_hip_update_scratch_bytes.argtypes = [u32, u32, u32, u32]
+        L.snappy_hip_update_ranges.restype = ctypes.c_int
+        L.snappy_hip_update_ranges.argtypes = [vp, u32, u32, vp, u32, vp, vp, u64, vp, vp, vp, u32, vp, u64, vp]
+        L.snappy_update_range_gpu.restype = ctypes.c_int
+        L.snappy_update_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64,
+                                              ctypes.POINTER(HostBufferContext), ctypes.POINTER(ProgramRuntime)]
         L.snappy_compress_gpu.restype = ctypes.c_int
         L.snappy_compress_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
                                           ctypes.POINTER(ProgramRuntime)]
@@ -350,6 +357,46 @@ def decompress_ranges(d_descs, count, d_ranges, range_count, d_status, max_block
     return d_scratch
 
 
+# overwriting byte ranges of one container (snappy_hip_update_ranges)
+WRITE_UNORDERED = 3
+UPDATE_REJECTED = 4
+WRITE_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8"), ("src", "<u8"), ("pad", "<u8")])   # snappy_hip_write
+
+
+def update_scratch_bytes(block_size, blocks, write_count, max_dirty_blocks):
+    """Scratch of snappy_hip_update_ranges on the current device (0 for a bad block size)."""
+    return int(lib().snappy_hip_update_scratch_bytes(block_size, blocks, write_count, max_dirty_blocks))
+
+
+def make_writes(entries, device="cuda"):
+    """entries: list of (offset, length, src) with src a device address (int), sorted by offset and disjoint -> device tensor
+    of snappy_hip_write."""
+    import torch
+    arr = np.zeros(max(len(entries), 1), dtype=WRITE_DTYPE)
+    for i, (off, length, src) in enumerate(entries):
+        arr[i] = (off, length, src, 0)
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
+def update_ranges(d_desc, total_len, block_size, d_writes, write_count, d_write_status, d_new_stream, d_new_offsets, d_new_stream_len,
+                  d_result, max_dirty_blocks, d_scratch=None, capacity=None):
+    """Enqueue snappy_hip_update_ranges on the current stream.  d_desc: make_stream_descs() tensor of ONE descriptor
+    (block_offsets filled in), d_writes: make_writes() tensor, d_write_status: device int32 tensor of write_count entries,
+    d_new_stream: device uint8 tensor (capacity: its size), d_new_offsets: device int64 tensor of num_blocks + 1 entries,
+    d_new_stream_len: device int64 tensor of one entry, d_result: device int32 tensor of two.  d_scratch: 256-byte aligned
+    device uint8 tensor (default: a fresh one).  Nothing is synchronised."""
+    import torch
+    nb = num_blocks(total_len, block_size)
+    if d_scratch is None:
+        d_scratch = torch.empty(update_scratch_bytes(block_size, nb, write_count, max_dirty_blocks), dtype=torch.uint8, device=d_new_stream.device)
+    _check(lib().snappy_hip_update_ranges(d_desc.data_ptr(), total_len, block_size, d_writes.data_ptr() if write_count else None, write_count,
+                                          d_write_status.data_ptr() if write_count else None, d_new_stream.data_ptr(),
+                                          d_new_stream.numel() if capacity is None else capacity, d_new_offsets.data_ptr(),
+                                          d_new_stream_len.data_ptr(), d_result.data_ptr(), max_dirty_blocks, d_scratch.data_ptr(),
+                                          d_scratch.numel(), _stream_handle(torch)), "snappy_hip_update_ranges")
+    return d_scratch
+
+
 # ---------------------------------------------------------------------------
 # drop-in pair (host buffers), driven the way dpu_snappy.c's main() drives the *_dpu functions
 # ---------------------------------------------------------------------------
@@ -418,3 +465,23 @@ def decompress_range_host(stream, offset, length, out_capacity=None):
     if out.buffer:
         libc().free(out.buffer)
     return st, data, rt.as_dict()
+
+
+def update_range_host(stream, offset, data, out_capacity=None):
+    """snappy_update_range_gpu on a whole framed file held in host memory: `data` over plaintext bytes [offset, offset +
+    len(data)) -> (status, new stream bytes, runtime dict).  out_capacity: as in compress_host."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
+    b = np.frombuffer(data, dtype=np.uint8).copy() if len(data) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
+    patch = HostBufferContext(b"<memory>", b.ctypes.data, b.ctypes.data, len(data), (1 << 64) - 1)
+    if out_capacity is None:
+        out = HostBufferContext(b"<memory>", None, None, 0, (1 << 64) - 1)
+    else:
+        buf = libc().malloc(max(1, out_capacity))
+        out = HostBufferContext(b"<memory>", buf, buf, 0, out_capacity)
+    rt = ProgramRuntime()
+    st = lib().snappy_update_range_gpu(ctypes.byref(inp), ctypes.byref(patch), offset, ctypes.byref(out), ctypes.byref(rt))
+    new = ctypes.string_at(out.buffer, out.length) if st == SNAPPY_OK else b""
+    if out.buffer:
+        libc().free(out.buffer)
+    return st, new, rt.as_dict()
