@@ -9,10 +9,12 @@
  * Parity pinning: this restatement is pinned, in BOTH directions, by the
  * reference's own committed test vectors (reference test/NAME.txt + test/NAME.snappy,
  * used by its `make test_host`, snappy/Makefile:54-56), copied as data fixtures
- * to tests/golden/.  See tests/test_oracle_golden.py.  The reference sources
- * themselves are not buildable in this image without writing stand-in headers
- * (snappy_compress.c:1-3 needs the UPMEM SDK <dpu.h>, dpu_snappy.h:4 needs the
- * un-vendored PIM-common "common.h"), so there is no oracle/_ref build.
+ * to tests/golden/ (tests/test_oracle_golden.py), and by the recorded results of
+ * the reference's own host codec over ~1,000 further cases: `make ref` here
+ * compiles the reference sources, read in place, against the stand-in headers of
+ * ref_standins/ (snappy_compress.c:1-3 needs the UPMEM SDK <dpu.h>, dpu_snappy.h:4
+ * the un-vendored PIM-common "common.h") into oracle/_ref/, and
+ * tests/test_reference_differential.py compares (tests/golden/reference_digests.json).
  *
  * Each function cites the reference file:line whose behaviour it restates.
  * The code is written position-indexed (offsets from block start) instead of
@@ -276,8 +278,10 @@ uint32_t oracle_read_header(const uint8_t *src, uint64_t n, uint32_t *total_len,
  * Whole-buffer decompress following snappy_decompress.c:218-289
  * (snappy_decompress_host) including its leniencies: literal and copy writes
  * are clipped at the end of input / output (:145-147, :174-175); a copy whose
- * source lies before the start of the whole output buffer is the only hard
- * error (:169-173).  `out_len` must be the uncompressed length from the header
+ * source lies before the start of the whole output buffer is the reference's
+ * only hard error (:169-173).  Refused in addition, because the reference's
+ * result is then not defined by the stream: a copy at offset 0 and a stream
+ * that ends before the output is complete.  `out_len` must be the uncompressed length from the header
  * (setup_decompression, :193-209).
  */
 int oracle_decompress(const uint8_t *src, uint64_t n, uint8_t *out, uint64_t out_len)
@@ -353,7 +357,10 @@ int oracle_decompress(const uint8_t *src, uint64_t n, uint8_t *out, uint64_t out
 			}
 		}
 	}
-	return ORACLE_OK;
+	/* The reference returns OK here whatever op is; out[op, out_len) then holds whatever its malloc (:207) returned.
+	 * Like the copy from unwritten bytes above, a result that is not a function of the stream is refused
+	 * (tests/test_reference_differential.py, case damaged/31: a 64-byte copy damaged into a 4-byte one). */
+	return (op == out_len) ? ORACLE_OK : ORACLE_INVALID_INPUT;
 }
 
 /*

@@ -229,6 +229,34 @@ struct GuardedCopy {
     ~GuardedCopy() { munmap(base, mapped); }
 };
 
+// An output of exactly `n` bytes that ends at an inaccessible page and starts behind one: a write of even one byte beyond
+// the window faults, and so does one a page or more in front of it.  The bytes between the front page and the window (less
+// than a page: the window's end is what is page-aligned) hold a pattern that intact() checks.
+struct GuardedOut {
+    static constexpr size_t kPage = 4096;
+    static constexpr uint8_t kFill = 0xA5;
+    uint8_t* base = nullptr;
+    size_t mapped = 0;
+    uint8_t* p = nullptr;
+    explicit GuardedOut(size_t n)
+    {
+        mapped = ((n + kPage - 1) / kPage + 2) * kPage;
+        base = (uint8_t*)mmap(nullptr, mapped, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (base == MAP_FAILED) abort();
+        p = base + mapped - kPage - n;
+        memset(base + kPage, kFill, (size_t)(p - (base + kPage)));
+        if (mprotect(base, kPage, PROT_NONE) != 0 || mprotect(base + mapped - kPage, kPage, PROT_NONE) != 0) abort();
+    }
+    bool intact() const
+    {
+        for (const uint8_t* q = base + kPage; q < p; ++q)
+            if (*q != kFill) return false;
+        return true;
+    }
+    ~GuardedOut() { munmap(base, mapped); }
+};
+constexpr int kWroteInFrontOfWindow = 100;   // status of the decode entries when GuardedOut::intact() fails
+
 // ---------------------------------------------------------------------------
 // C entry points used by tests/test_emulated_kernels.py
 // ---------------------------------------------------------------------------
@@ -333,10 +361,11 @@ uint64_t emu_compress(const uint8_t* in, uint64_t n, uint32_t block_size, uint8_
     return emu_compress_variant(in, n, block_size, stream, stream_cap, 12503);
 }
 
-// Runs index_streams_kernel + decompress_blocks_kernel on the emulator.
-// Returns 0 on success, 1 if any block (or the chain) is invalid.
+// Runs index_streams_kernel + decompress_blocks_kernel on the emulator; K2 writes into a GuardedOut of exactly total_len
+// bytes, which is then copied to `out` (total_len bytes).
+// Returns 0 on success, 1 if any block (or the chain) is invalid, 100 if K2 wrote in front of its output.
 int emu_decompress_variant(const uint8_t* stream_in, uint64_t stream_len, uint32_t total_len, uint32_t block_size,
-                           uint32_t header_len, uint8_t* out, int variant)
+                           uint32_t header_len, uint8_t* out_user, int variant)
 {
     GuardedCopy guarded(stream_in, stream_len);                  // K2 and the walk must not read one byte beyond the stream
     const uint8_t* stream = guarded.p;
@@ -349,6 +378,7 @@ int emu_decompress_variant(const uint8_t* stream_in, uint64_t stream_len, uint32
     if (result[0] != 0 || result[1] != nb) return 1;
     std::vector<uint32_t> status(nb, 9);
     uint32_t k2_counter = 0;
+    GuardedOut guarded_out(total_len);
     snappy_hip::K2Batch kb{};
     kb.count = 1;
     kb.first_block[0] = 0;
@@ -357,13 +387,42 @@ int emu_decompress_variant(const uint8_t* stream_in, uint64_t stream_len, uint32
     kb.stream_len[0] = stream_len;
     kb.block_offsets[0] = boff.data();
     kb.total_len[0] = total_len;
-    kb.out[0] = out;
+    kb.out[0] = guarded_out.p;
     kb.status[0] = status.data();
     (void)variant;                                                       // (one decoder: the per-window batch)
     emu::launch(nb < 3 ? nb : 3, 64, [&] { snappy_hip::decompress_blocks_kernel(kb, block_size, &k2_counter); });
+    if (!guarded_out.intact()) return kWroteInFrontOfWindow;
+    memcpy(out_user, guarded_out.p, total_len);
     for (uint32_t i = 0; i < nb; ++i)
         if (status[i] != 0) return 1;
     return 0;
+}
+
+// ONE block decoded alone, as a job of its own: the block whose u32 size word is at stream + at, into a GuardedOut of exactly
+// out_len bytes (copied to out_user afterwards) -- an overrun into what would be a neighbouring block's window faults here
+// instead of being overwritten by the neighbour later.  The stream ends at an inaccessible page too.
+// Returns the block's status (0 / 1), or 100 if K2 wrote in front of the window.
+int emu_decompress_block(const uint8_t* stream_in, uint64_t stream_len, uint64_t at, uint32_t out_len, uint8_t* out_user)
+{
+    if (out_len == 0) return 1;
+    GuardedCopy guarded(stream_in, stream_len);
+    GuardedOut guarded_out(out_len);
+    uint64_t boff = at;
+    uint32_t status = 9, k2_counter = 0;
+    snappy_hip::K2Batch kb{};
+    kb.count = 1;
+    kb.first_block[0] = 0;
+    kb.first_block[1] = 1;
+    kb.stream[0] = guarded.p;
+    kb.stream_len[0] = stream_len;
+    kb.block_offsets[0] = &boff;
+    kb.total_len[0] = out_len;
+    kb.out[0] = guarded_out.p;
+    kb.status[0] = &status;
+    emu::launch(1, 64, [&] { snappy_hip::decompress_blocks_kernel(kb, out_len, &k2_counter); });
+    if (!guarded_out.intact()) return kWroteInFrontOfWindow;
+    memcpy(out_user, guarded_out.p, out_len);
+    return (int)status;
 }
 
 // The size chain in parallel segments (chain_anchor / chain_walk / chain_finish kernels) followed by the serial walk for

@@ -41,6 +41,8 @@ def lib():
         L.emu_decompress_variant.restype = ctypes.c_int
         L.emu_decompress_variant.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                              ctypes.c_void_p, ctypes.c_int]
+        L.emu_decompress_block.restype = ctypes.c_int
+        L.emu_decompress_block.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
         L.emu_verify_index.restype = None
         L.emu_verify_index.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.c_uint32, ctypes.c_void_p]
@@ -65,9 +67,18 @@ def compress(data, block_size=32768, variant=43503):   # the product default for
 
 def decompress(stream, total_len, block_size, header_len, variant=3):   # 3 = the product's per-window batch decoder
     a = np.frombuffer(stream, dtype=np.uint8).copy()
-    out = np.zeros(max(total_len, 1) + 16, dtype=np.uint8)
+    out = np.zeros(max(total_len, 1), dtype=np.uint8)          # no slack: K2 gets exactly total_len bytes, between inaccessible pages
     st = lib().emu_decompress_variant(a.ctypes.data, a.size, total_len, block_size, header_len, out.ctypes.data, variant)
     return st, out[:total_len].tobytes()
+
+
+def decompress_block(stream, at, out_len):
+    """ONE block (size word at stream[at]) decoded alone into exactly out_len bytes between inaccessible pages
+    -> (status, bytes); status 100: K2 wrote in front of the window.  A write behind it faults: call from a child process."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy()
+    out = np.zeros(max(out_len, 1), dtype=np.uint8)
+    st = lib().emu_decompress_block(a.ctypes.data, a.size, at, out_len, out.ctypes.data)
+    return st, out[:out_len].tobytes()
 
 
 def verify_index(stream, offsets, total_len, block_size, header_len):
