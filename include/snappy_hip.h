@@ -367,6 +367,87 @@ SNAPPY_HIP_API int snappy_hip_update_ranges(const snappy_hip_stream_desc *d_desc
                              uint64_t *d_new_stream_len, uint32_t *d_result, uint32_t max_dirty_blocks, void *d_scratch,
                              uint64_t scratch_bytes, void *stream);
 
+/* ---- 1a. batches of raw Snappy streams, described on the device ---------- */
+
+/*
+ * The ORIGINAL ("raw") Snappy format: varint32(uncompressed length) followed by ONE element stream whose back-references may
+ * reach back as far as the stream is long -- what Parquet and ORC pages, Arrow IPC buffers, RPC payloads and `snzip -t raw`
+ * hold, and what every other Snappy library reads.  Many independent buffers, each described by one 32-byte item that the
+ * kernels read from DEVICE memory (the host never sees the items), for both directions.
+ *
+ * ONE RAW STREAM IS ONE WAVEFRONT'S WORK: element boundaries in a raw stream cannot be found without parsing it, so a stream
+ * cannot be split among wavefronts the way the framed format's blocks are.  From this project's figure of 0.5-0.6 ms per
+ * 32 KiB block and wavefront that is an estimated 55-65 MB/s per stream (an estimate, not a measurement of this kernel); the
+ * device is full only with thousands of items.  Decoding ONE large raw file on the GPU is therefore slower than the host
+ * mode.  That is a property of the format.  (Compression has no such limit: the fragments of one item compress in parallel.)
+ */
+typedef struct snappy_hip_raw_item {
+	const void *src;        /* device: the input of this item, any alignment            */
+	uint64_t src_len;       /* bytes                                                    */
+	void *dst;              /* device: where the output goes, any alignment             */
+	uint64_t dst_capacity;  /* bytes available at dst                                   */
+} snappy_hip_raw_item;
+#define SNAPPY_HIP_RAW_DST_TOO_SMALL 5u
+#define SNAPPY_HIP_RAW_TOO_LARGE     6u
+/* The longest stream and the longest output the decoder takes: 2 GiB - 4 KiB.  Its cursors are 32 bits wide; the sum it forms
+ * that grows fastest is "output so far + output of one 64-byte window" <= 2 * MAX_LEN + 1408, which must stay below 2^32
+ * (csrc/snappy_raw.hpp has the whole argument). */
+#define SNAPPY_HIP_RAW_MAX_LEN 0x7ffff000ull
+
+/*
+ * Item i's src[0, src_len) is one raw Snappy stream from any compressor; it is decoded to dst.  d_items, d_out_len, d_status:
+ * device arrays of `count` entries.  Per item, always written: d_status[i] and d_out_len[i].
+ *   SNAPPY_HIP_BLOCK_OK            dst[0, d_out_len[i]) holds the plaintext.  A stream of length 0 is OK iff nothing follows
+ *                                  its header.
+ *   SNAPPY_HIP_BLOCK_INVALID       src is null, or the header is malformed (a varint32 as Google's decoder reads it: at most
+ *                                  5 bytes, the fifth below 16, inside src_len): d_out_len[i] = 0.  Or the elements do not
+ *                                  decode under the strictness of snappy_hip_decompress_blocks: a zero offset, a reference
+ *                                  before the first output byte, an element or literal payload running past src_len, output
+ *                                  beyond the header's length, a stream that ends before or after the output is complete;
+ *                                  the contents of dst[0, length) are then unspecified.  All four element types, offsets of
+ *                                  any size, literals of any length the header allows.
+ *   SNAPPY_HIP_RAW_DST_TOO_SMALL   the header's length exceeds dst_capacity (a null dst counts as capacity 0): not one byte
+ *                                  written.
+ *   SNAPPY_HIP_RAW_TOO_LARGE       src_len or the header's length exceeds SNAPPY_HIP_RAW_MAX_LEN: nothing written.
+ * d_out_len[i] = the header's length whenever the header parses, so a first call with capacities of 0 sizes the outputs.
+ * Whatever the streams hold, nothing outside [dst, dst + length) of any item is written.  The outputs must not overlap each
+ * other or any source.  count == 0 is OK and launches nothing.
+ * The call only enqueues work on `stream`; it never synchronises, never calls the allocator and needs no scratch.
+ * SNAPPY_HIP_ERR_ARG (host side): null arrays with count > 0.
+ */
+SNAPPY_HIP_API int snappy_hip_raw_decompress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint64_t *d_out_len,
+                                    uint32_t *d_status, void *stream);
+
+/*
+ * Item i's src[0, src_len) is plaintext; its output is varint(src_len) followed by the elements K1 produces for each
+ * block_size FRAGMENT of it in order -- byte for byte tools/to_raw_snappy.py convert() of the framed stream
+ * snappy_hip_compress_blocks + snappy_hip_compact give for the same bytes and block size.  A fragment is one K1 block: the
+ * block_size limits of snappy_hip_compress_blocks, a hash table of its own, no reference across fragments (which is what
+ * Google's compressor does with its 64 KiB fragments, so any Snappy decoder accepts the result).  The fragments of one item
+ * compress in parallel.  An empty item gives the one byte 00.
+ * Per item, always written:
+ *   SNAPPY_HIP_BLOCK_OK            d_out_len[i] = bytes written to dst.
+ *   SNAPPY_HIP_RAW_DST_TOO_SMALL   d_out_len[i] = the size it needs; not one byte of dst is written.
+ *   SNAPPY_HIP_RAW_TOO_LARGE       src_len >= 4 GiB, or the item's fragments lie beyond max_fragments of the call (the scratch
+ *                                  holds no more slots; the items in front of it complete).  d_out_len[i] = 0.
+ *   SNAPPY_HIP_BLOCK_INVALID       a null src with src_len > 0.  d_out_len[i] = 0.
+ * d_result[0] = the fragments the whole batch needs (saturated at 2^32 - 1), so that a caller can size a second call;
+ * d_result[1] = the number of items that are OK.
+ * snappy_hip_raw_compress_bound: a dst_capacity that always suffices for an item of src_len bytes.
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_raw_compress_scratch_bytes(block_size, count,
+ * max_fragments) bytes, not shared with a launch that runs concurrently; contents need not be initialised.  It holds one
+ * u64 per item and, per fragment, a u32, a u64 and one compressed slot (snappy_hip_slot_stride).
+ * The call only enqueues work on `stream`; the verdicts stay on the device.
+ * SNAPPY_HIP_ERR_ARG (host side): null arrays with count > 0, a bad block size, a scratch that is misaligned or too small.
+ * The fragments are compressed by K1's LDS-table form (as the update's dirty blocks are); a global-table variant for very
+ * large batches is not part of this interface.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_raw_compress_bound(uint64_t src_len, uint32_t block_size);
+SNAPPY_HIP_API uint64_t snappy_hip_raw_compress_scratch_bytes(uint32_t block_size, uint32_t count, uint32_t max_fragments);
+SNAPPY_HIP_API int snappy_hip_raw_compress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t block_size,
+                                  uint32_t max_fragments, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result,
+                                  void *d_scratch, uint64_t scratch_bytes, void *stream);
+
 /* ---- 1b. drop-in level: one byte range of a framed file ----------------- */
 
 /*
@@ -392,6 +473,29 @@ SNAPPY_HIP_API snappy_status snappy_decompress_range_gpu(struct host_buffer_cont
  */
 SNAPPY_HIP_API snappy_status snappy_update_range_gpu(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
                                       struct host_buffer_context *output, struct program_runtime *runtime);
+
+/* ---- 1c. drop-in level: one buffer of the raw Snappy format -------------- */
+
+/*
+ * input (plaintext, less than 4 GiB) as ONE raw Snappy stream -- varint(length) + the elements of its block_size fragments,
+ * what every other Snappy library reads -- written to output (as in snappy_compress_gpu: realloc'd to the stream's size, or
+ * used as is when output->max is finite, SNAPPY_BUFFER_TOO_SMALL if it does not fit).  One item through
+ * snappy_hip_raw_compress_batch on the current device; no sharding.  The bytes are tools/to_raw_snappy.py convert() of what
+ * snappy_compress_gpu writes for the same input and block size.  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_compress_raw_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                      uint32_t block_size, struct program_runtime *runtime);
+
+/*
+ * The raw Snappy stream in input (the whole file: input->buffer at its first byte, input->length = file size; from any
+ * compressor) decoded to output (realloc'd to the header's length, or used as is when output->max is finite,
+ * SNAPPY_BUFFER_TOO_SMALL if it does not fit).  One item through snappy_hip_raw_decompress_batch on the current device: ONE
+ * wavefront decodes the whole stream, so for one large file this is slower than the host mode (see 1a).
+ * SNAPPY_INVALID_INPUT: a malformed header, a stream or length above SNAPPY_HIP_RAW_MAX_LEN, or elements that do not decode.
+ * Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_raw_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                        struct program_runtime *runtime);
 
 #ifdef __cplusplus
 }

@@ -910,6 +910,134 @@ snappy_status update_range_gpu_body(struct host_buffer_context* input, struct ho
     return SNAPPY_OK;
 }
 
+// The raw ("original") Snappy format, one buffer each way on the current device: one item through the batch calls of
+// snappy_raw.hpp, no sharding.  Phased and synchronous like the range call above.
+// claims the output buffer for `n` bytes: the caller's (finite max) or ours (snappy_compress_gpu's rule)
+snappy_status raw_output_buffer(struct host_buffer_context* output, uint64_t n)
+{
+    const bool caller_owned = output->buffer && output->max != ~0UL;
+    if (caller_owned && output->max < n) {
+        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold %lu bytes\n", (unsigned long)output->max, (unsigned long)n);
+        return SNAPPY_BUFFER_TOO_SMALL;
+    }
+    if (!caller_owned) {
+        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, n ? n : 1);
+        if (!nbuf) {
+            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)n);
+            return SNAPPY_BUFFER_TOO_SMALL;
+        }
+        output->buffer = nbuf;
+    }
+    return SNAPPY_OK;
+}
+
+struct RawVerdict {            // what one item's call leaves on the device
+    uint64_t out_len;
+    uint32_t status;
+    uint32_t result[2];
+    uint32_t pad;
+};
+
+// compress = true: plaintext -> raw stream at `block_size` fragments; false: raw stream -> plaintext
+snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
+                           struct program_runtime* runtime)
+{
+    double t0 = now_seconds();
+    if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
+    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+    const uint64_t in_len = input->length;
+    uint64_t capacity = 0, scratch_bytes = 0;
+    uint32_t fragments = 0;
+    if (compress) {
+        if (!block_size_ok(block_size)) {
+            fprintf(stderr, "snappy_hip: block size %u is outside 1..65535\n", block_size);
+            return SNAPPY_INVALID_INPUT;
+        }
+        if (in_len >> 32) {
+            fprintf(stderr, "snappy_hip: a raw Snappy stream holds less than 4 GiB\n");
+            return SNAPPY_INVALID_INPUT;
+        }
+        fragments = (uint32_t)snappy_hip_num_blocks(in_len, block_size);
+        capacity = snappy_hip_raw_compress_bound(in_len, block_size);
+        scratch_bytes = snappy_hip_raw_compress_scratch_bytes(block_size, 1, fragments);
+    } else {
+        uint32_t length = 0;
+        const uint32_t hdr = get_varint32(input->buffer, in_len, &length);   // (the device reads it again, by Google's rule)
+        if (!hdr) {
+            fprintf(stderr, "Failed to read the stream header\n");
+            return SNAPPY_INVALID_INPUT;
+        }
+        if (in_len > SNAPPY_HIP_RAW_MAX_LEN || length > SNAPPY_HIP_RAW_MAX_LEN) {
+            fprintf(stderr, "snappy_hip: raw streams of more than %llu bytes are not decoded\n", (unsigned long long)SNAPPY_HIP_RAW_MAX_LEN);
+            return SNAPPY_INVALID_INPUT;
+        }
+        capacity = length;
+        if (snappy_status st = raw_output_buffer(output, capacity)) return st;
+    }
+    output->length = 0;
+    output->curr = output->buffer;
+    if (snappy_hip_device_count() <= 0) {
+        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
+        return SNAPPY_INVALID_INPUT;
+    }
+    runtime->pre += now_seconds() - t0;
+
+    DeviceBuffers dev;
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    snappy_hip_raw_item* d_item = nullptr;
+    RawVerdict* d_verdict = nullptr;
+    double t = now_seconds();
+    if (dev.alloc((void**)&d_in, in_len) || dev.alloc((void**)&d_out, capacity) || dev.alloc((void**)&d_item, sizeof(snappy_hip_raw_item)) ||
+        dev.alloc((void**)&d_verdict, sizeof(RawVerdict)) || dev.alloc((void**)&d_scratch, scratch_bytes))
+        return report("device allocation");
+    runtime->d_alloc = now_seconds() - t;
+    t = now_seconds();
+    if (warm_up_device()) return report("code object load");
+    runtime->load = now_seconds() - t;
+    const snappy_hip_raw_item item{d_in, in_len, d_out, capacity};
+    t = now_seconds();
+    if ((in_len && hipMemcpy(d_in, input->buffer, in_len, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(d_item, &item, sizeof item, hipMemcpyHostToDevice) != hipSuccess) {
+        g_last_error = "hipMemcpy to the device";
+        return report("host-to-device copy");
+    }
+    runtime->copy_in = now_seconds() - t;
+    t = now_seconds();
+    const int launched = compress ? snappy_hip_raw_compress_batch(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
+                                                                  d_verdict->result, d_scratch, scratch_bytes, nullptr)
+                                  : snappy_hip_raw_decompress_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr);
+    if (launched != SNAPPY_HIP_OK) return report("raw batch launch");
+    if (hipDeviceSynchronize() != hipSuccess) {
+        g_last_error = "hipDeviceSynchronize after the raw batch";
+        return report("raw batch");
+    }
+    runtime->run = now_seconds() - t;
+    t = now_seconds();
+    RawVerdict v{};
+    if (hipMemcpy(&v, d_verdict, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_last_error = "hipMemcpy to the host";
+        return report("device-to-host copy");
+    }
+    if (v.status != SNAPPY_HIP_BLOCK_OK || v.out_len > capacity) {
+        fprintf(stderr, "snappy_hip: the raw stream cannot be %s (status %u)\n", compress ? "written" : "decoded", v.status);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (compress)
+        if (snappy_status st = raw_output_buffer(output, v.out_len)) return st;
+    if (v.out_len && hipMemcpy(output->buffer, d_out, v.out_len, hipMemcpyDeviceToHost) != hipSuccess) {
+        g_last_error = "hipMemcpy to the host";
+        return report("device-to-host copy");
+    }
+    runtime->copy_out = now_seconds() - t;
+    t = now_seconds();
+    for (void* p : dev.mem) (void)hipFree(p);
+    dev.mem.clear();
+    runtime->d_free = now_seconds() - t;
+    output->length = v.out_len;
+    output->curr = output->buffer + v.out_len;
+    return SNAPPY_OK;
+}
+
 // The exported pair: one call at a time per process (the cached pipeline streams and their page-locked scratch are per
 // process; the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618), the caller's
 // current HIP device restored on every return path, and no C++ exception crosses the C boundary.
@@ -957,6 +1085,17 @@ snappy_status snappy_update_range_gpu(struct host_buffer_context* input, struct 
                                       struct host_buffer_context* output, struct program_runtime* runtime)
 {
     return entry_guard([&] { return update_range_gpu_body(input, patch, offset, output, runtime); });
+}
+
+snappy_status snappy_compress_raw_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
+                                      struct program_runtime* runtime)
+{
+    return entry_guard([&] { return raw_gpu_body(true, input, output, block_size, runtime); });
+}
+
+snappy_status snappy_decompress_raw_gpu(struct host_buffer_context* input, struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return raw_gpu_body(false, input, output, 0, runtime); });
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 #include "snappy_kernels.hpp"
 #include "snappy_ranges.hpp"
 #include "snappy_update.hpp"
+#include "snappy_raw.hpp"
 
 namespace {
 
@@ -958,6 +959,91 @@ int snappy_hip_update_ranges(const snappy_hip_stream_desc* d_desc, uint32_t tota
     if (nb)
         hipLaunchKernelGGL(snappy_hip::merge_stream_kernel, dim3(nb), dim3(256), 0, st, desc, nb, ctl, rank, scratch + l.cslots, stride,
                            d_new_offsets, d_new_stream);
+    HIP_TRY(hipGetLastError());
+    return SNAPPY_HIP_OK;
+}
+
+// ---- batches of raw Snappy streams (snappy_raw.hpp) ----
+int snappy_hip_raw_decompress_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint64_t* d_out_len, uint32_t* d_status, void* stream)
+{
+    static_assert(sizeof(snappy_hip_raw_item) == sizeof(snappy_hip::RawItem) && sizeof(snappy_hip::RawItem) == 32, "snappy_hip_raw_item layout");
+    static_assert(SNAPPY_HIP_RAW_MAX_LEN == snappy_hip::kRawMaxLen && SNAPPY_HIP_RAW_MAX_LEN >= (1ull << 30), "SNAPPY_HIP_RAW_MAX_LEN");
+    static_assert(SNAPPY_HIP_RAW_DST_TOO_SMALL == snappy_hip::kRawDstTooSmall && SNAPPY_HIP_RAW_TOO_LARGE == snappy_hip::kRawTooLarge, "raw status codes");
+    if (count == 0) return SNAPPY_HIP_OK;
+    if (!d_items || !d_out_len || !d_status) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    hipStream_t st = (hipStream_t)stream;
+    WorkCounter wc;
+    if (int rc = next_work_counter(&wc, st)) return rc;
+    const uint32_t grid = std::min(range_grid_cap(), count);
+    hipLaunchKernelGGL(snappy_hip::raw_decompress_kernel, dim3(grid), dim3(64), 0, st, reinterpret_cast<const snappy_hip::RawItem*>(d_items), count,
+                       d_out_len, d_status, wc.ptr);
+    const hipError_t launched = hipGetLastError();
+    if (int rc = work_counter_launched(wc, st)) return rc;
+    HIP_TRY(launched);
+    return SNAPPY_HIP_OK;
+}
+
+uint64_t snappy_hip_raw_compress_bound(uint64_t src_len, uint32_t block_size)
+{
+    if (!block_size_ok(block_size)) return 0;
+    // per fragment of n bytes K1 writes at most 32 + n + n / 6 bytes of elements (what snappy_hip_slot_stride reserves)
+    const uint64_t fragments = snappy_hip_num_blocks(src_len, block_size);
+    return 5 + fragments * 32 + src_len + src_len / 6;
+}
+
+uint64_t snappy_hip_raw_compress_scratch_bytes(uint32_t block_size, uint32_t count, uint32_t max_fragments)
+{
+    if (!block_size_ok(block_size)) return 0;
+    return snappy_hip::raw_layout(count, max_fragments, snappy_hip_slot_stride(block_size)).total;
+}
+
+int snappy_hip_raw_compress_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t block_size, uint32_t max_fragments,
+                                  uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch, uint64_t scratch_bytes,
+                                  void* stream)
+{
+    if (!block_size_ok(block_size)) return fail(SNAPPY_HIP_ERR_ARG, "block_size must be 1..65535");
+    if (!d_result || (count && (!d_items || !d_out_len || !d_status))) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    const uint32_t stride = snappy_hip_slot_stride(block_size);
+    const snappy_hip::RawLayout l = snappy_hip::raw_layout(count, max_fragments, stride);
+    if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_raw_compress_scratch_bytes)");
+    if (int rc = check_knobs()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
+    uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.prefix);
+    uint32_t* frag_bytes = reinterpret_cast<uint32_t*>(scratch + l.frag_bytes);
+    uint64_t* place = reinterpret_cast<uint64_t*>(scratch + l.place);
+    const auto* items = reinterpret_cast<const snappy_hip::RawItem*>(d_items);
+    hipLaunchKernelGGL(snappy_hip::raw_plan_kernel, dim3(1), dim3(1024), 0, st, items, count, block_size, max_fragments, d_out_len, d_status,
+                       d_result, ctl, prefix);
+    HIP_TRY(hipGetLastError());
+    if (count == 0 || max_fragments == 0) {
+        if (count)      // (no slot: only empty items can be OK)
+            hipLaunchKernelGGL(snappy_hip::raw_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, items, count, prefix, frag_bytes, place,
+                               d_out_len, d_status, d_result);
+        HIP_TRY(hipGetLastError());
+        return SNAPPY_HIP_OK;
+    }
+    {
+        WorkCounter wc;
+        if (int rc = next_work_counter(&wc, st)) return rc;
+        const uint32_t waves = std::min(launch_shape::update_resident_waves(device_shape(), lds_table_wave_bytes(block_size)), max_fragments);
+        if (k1_stream_forms(block_size) & 1)
+            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<3>, dim3(waves), dim3(64), snappy_hip::lds_table_stream_lds_bytes(block_size),
+                               st, items, count, block_size, ctl, prefix, frag_bytes, scratch + l.slots, stride, wc.ptr);
+        else
+            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<2>, dim3(waves), dim3(64),
+                               snappy_hip::lds_table_kernel_lds_bytes(block_size, true), st, items, count, block_size, ctl, prefix, frag_bytes,
+                               scratch + l.slots, stride, wc.ptr);
+        const hipError_t launched = hipGetLastError();
+        if (int rc = work_counter_launched(wc, st)) return rc;
+        HIP_TRY(launched);
+    }
+    hipLaunchKernelGGL(snappy_hip::raw_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, items, count, prefix, frag_bytes, place, d_out_len,
+                       d_status, d_result);
+    hipLaunchKernelGGL(snappy_hip::raw_gather_kernel, dim3(std::min(max_fragments, 32768u)), dim3(256), 0, st, items, count, ctl, prefix, frag_bytes,
+                       place, scratch + l.slots, stride, d_status);
     HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
 }

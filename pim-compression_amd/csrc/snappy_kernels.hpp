@@ -1753,6 +1753,10 @@ __device__ __forceinline__ uint64_t window_value(const WindowLoad& r) { return (
 // lanes whose element cannot be valid here (over-long literal, header or literal payload running past the block's compressed
 // size).  Per-lane conditions of this decoder are kept as LANE MASKS built from single compares and combined with scalar
 // logic: a ballot of a compound bool costs a v_cndmask + v_cmp on top of the compares.
+// kRaw (snappy_raw.hpp: one raw Snappy stream of up to kRawMaxLen bytes instead of one block): a literal is as long as its
+// length field says -- 0xFFFFFFFF + 1 wraps to 0 and is rejected with the other zero lengths -- and the test against the
+// compressed size is made in 64 bits, so that no length field can wrap it.
+template <bool kRaw = false>
 __device__ __forceinline__ void predecode_window(uint64_t w, uint32_t pos, uint32_t csz, uint32_t& type, uint32_t& hdr, uint32_t& olen,
                                                  uint32_t& off, uint32_t& consumed, unsigned long long& rejected)
 {
@@ -1767,10 +1771,12 @@ __device__ __forceinline__ void predecode_window(uint64_t w, uint32_t pos, uint3
     off = lit ? 0u : ((type == 1) ? c1_off : ((type == 2) ? (next4 & 0xffffu) : next4));
     const bool long_lit = lit && v >= 60u;                                       // :250-255, :64-74: v - 59 = 1..4 length bytes
     const uint32_t raw = next4 & (0xffffffffu >> ((63u - v) * 8u & 31u));       // shift 24, 16, 8, 0 (only read when long_lit)
-    olen = long_lit ? ((raw < 65536u) ? raw + 1u : 0u) : olen;                   // blocks are < 64 KiB
+    if constexpr (kRaw) olen = long_lit ? raw + 1u : olen;
+    else olen = long_lit ? ((raw < 65536u) ? raw + 1u : 0u) : olen;              // blocks are < 64 KiB
     hdr = long_lit ? v - 58u : hdr;
-    consumed = hdr + (lit ? olen : 0u);
-    rejected = __ballot(olen == 0) | __ballot(pos + consumed > csz);
+    consumed = hdr + (lit ? olen : 0u);                                          // (kRaw: may wrap, in rejected lanes only)
+    if constexpr (kRaw) rejected = __ballot(olen == 0) | __ballot((uint64_t)pos + hdr + (lit ? olen : 0u) > csz);
+    else rejected = __ballot(olen == 0) | __ballot(pos + consumed > csz);
 }
 
 
@@ -1884,20 +1890,27 @@ constexpr uint32_t kK2WalkLevels = SNAPPY_K2_WALK_LEVELS;
 // size prefix is at stream + at is decoded into win[0, out_len) -- written in place, back-references read from there, nothing
 // outside it written whatever the stream holds -- with `stage` (kK2StageBytes of LDS) for one window's output.  Returns
 // kBlockOk / kBlockInvalid.  Wave-uniform arguments; every lane of the wavefront calls it.
+// kRaw = true (snappy_raw.hpp): ONE raw Snappy stream instead -- no size word, the elements are stream[at, stream_len);
+// literals of any length; stream_len and out_len up to kRawMaxLen, for which none of the 32-bit cursors below can wrap; a
+// long literal's run-on copied 16 bytes per lane and step.  One body for both, so that the block form stays what it was.
+template <bool kRaw = false>
 __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint64_t stream_len, uint64_t at, uint8_t* win,
                                                    uint32_t out_len, lds_bytes_t stage)
 {
     const uint32_t lane = threadIdx.x;
     uint32_t st = kBlockOk;
     uint32_t csz = 0;
-    if (at + 4 > stream_len) {
+    if constexpr (kRaw) {
+        csz = (uint32_t)(stream_len - at);                           // (the caller has checked at <= stream_len <= kRawMaxLen)
+    } else if (at + 4 > stream_len) {
         st = kBlockInvalid;
     } else {
         csz = uld32(stream + at);                                    // snappy_decompress.c:229-230
         if (at + 4 + (uint64_t)csz > stream_len) st = kBlockInvalid;
     }
-    const uint8_t* __restrict__ src = stream + at + 4;
-    const uint64_t avail = (st == kBlockOk) ? stream_len - (at + 4) : 0;
+    const uint32_t skip = kRaw ? 0u : 4u;
+    const uint8_t* __restrict__ src = stream + at + skip;
+    const uint64_t avail = (st == kBlockOk) ? stream_len - (at + skip) : 0;
 
     uint32_t g = 0;             // window base, multiple of 64 (compressed offset)
     uint32_t cp = 0, op = 0;    // compressed / output cursors
@@ -1940,7 +1953,7 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
             const uint32_t wlim = wend - g;
             uint32_t e_type, e_hdr, e_len, e_consumed;
             unsigned long long REJ;
-            predecode_window(w0, g + lane, csz, e_type, e_hdr, e_len, offv, e_consumed, REJ);
+            predecode_window<kRaw>(w0, g + lane, csz, e_type, e_hdr, e_len, offv, e_consumed, REJ);
             const uint32_t advv = __builtin_amdgcn_inverse_ballot_w64(REJ) ? 64u : e_consumed;
             uint32_t s = cp - g;
             unsigned long long E = 0;
@@ -2045,9 +2058,24 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                     const uint8_t* __restrict__ p = src + g + 128u;
                     uint8_t* d = win + (uint32_t)(dbase + 128u);     // dbase may be "negative" (mod 2^32): add before widening
                     const uint32_t rest = pe - 128u;
-                    uint32_t i = 4 * lane;
-                    for (; i + 4 <= rest; i += 4 * kWave) st32(d + i, ld32(p + i));
-                    for (; i < rest; ++i) d[i] = p[i];
+                    if constexpr (kRaw) {
+                        // a literal of up to the whole stream: 16 bytes per lane and step, the last step clamped back to end
+                        // at `rest` (it rewrites bytes with the same values)
+                        if (rest >= 16u) {
+                            for (uint32_t i = 16u * lane; i < rest; i += 16u * kWave) {
+                                const uint32_t o = i < rest - 16u ? i : rest - 16u;
+                                uint4 v;
+                                __builtin_memcpy(&v, p + o, 16);
+                                __builtin_memcpy(d + o, &v, 16);
+                            }
+                        } else if (lane < rest) {
+                            d[lane] = p[lane];
+                        }
+                    } else {
+                        uint32_t i = 4 * lane;
+                        for (; i + 4 <= rest; i += 4 * kWave) st32(d + i, ld32(p + i));
+                        for (; i < rest; ++i) d[i] = p[i];
+                    }
                 }
             }
             // ---- copies, second part.  The far copies land in the stage.  Near ones (source wholly inside the stage) go

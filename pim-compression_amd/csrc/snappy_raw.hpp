@@ -1,0 +1,271 @@
+// snappy_raw.hpp -- batches of ORIGINAL ("raw") Snappy streams, described on the device (snappy_hip_raw_decompress_batch,
+// snappy_hip_raw_compress_batch, include/snappy_hip.h).
+//
+// A raw stream is varint32(uncompressed length) + ONE element stream whose back-references may reach back as far as the
+// stream is long: what Parquet / ORC pages, Arrow IPC buffers and `snzip -t raw` hold.  An item is (src, src_len, dst,
+// dst_capacity), read from device memory.
+//   * decode: raw_decompress_kernel (persistent wavefronts, one counter, as decompress_ranges_kernel): a wavefront draws an
+//     item, reads its header and decodes the whole stream with K2's own decoder in its raw form (k2_decode_block<true>:
+//     literals of any length, 64-bit bounds against the stream, wide run-on copies).  Element boundaries of a raw stream cannot
+//     be found without parsing it, so ONE STREAM IS ONE WAVEFRONT'S WORK; the device is full only with thousands of items.
+//   * compress: a FRAGMENT is block_size bytes of an item, compressed as one K1 block (own hash table, no reference across
+//     fragments -- what Google's compressor does with its 64 KiB fragments, so any decoder accepts the result).  The work unit
+//     is the pair (item, fragment), found from the exclusive prefix of the items' fragment counts by binary search.  Four
+//     kernels, the update's pipeline: raw_plan_kernel (one workgroup: validates the items, counts and prefixes the fragments),
+//     raw_compress_fragments_kernel (persistent wavefronts, K1's LDS-table form, fragment f into slot f of the scratch),
+//     raw_sizes_kernel (a wavefront per item: size, capacity verdict, header, each fragment's place in dst) and
+//     raw_gather_kernel (a workgroup per fragment: the payload without its u32 size word, any alignment on both sides).
+//     Item i's output is byte for byte tools/to_raw_snappy.py convert() of the framed stream of the same plaintext.
+#pragma once
+#include "snappy_update.hpp"
+
+namespace snappy_hip {
+
+constexpr uint32_t kRawDstTooSmall = 5;      // SNAPPY_HIP_RAW_DST_TOO_SMALL
+constexpr uint32_t kRawTooLarge = 6;         // SNAPPY_HIP_RAW_TOO_LARGE
+// The longest stream and the longest output the decoder takes (SNAPPY_HIP_RAW_MAX_LEN).  K2's cursors are 32 bits wide.  With
+// csz, out_len <= M: a compressed cursor never exceeds csz + 200 (window base + 128 + 72 in issue()); an element predecode
+// accepted ends inside the stream (64-bit test), so a literal is at most M long; one window's output `total` is at most that
+// literal + 1408 bytes of copies, and op <= out_len when `op + total > out_len` is evaluated: op + total <= 2 M + 1408, which
+// must stay below 2^32.  M = 2^31 - 4096 is the largest page multiple that does.
+constexpr uint64_t kRawMaxLen = 0x7ffff000ull;
+
+struct RawItem {               // must match snappy_hip_raw_item (include/snappy_hip.h)
+    const uint8_t* src;
+    uint64_t src_len;
+    uint8_t* dst;
+    uint64_t dst_capacity;
+};
+
+__global__ __launch_bounds__(64) void raw_decompress_kernel(const RawItem* __restrict__ items, uint32_t count, uint64_t* __restrict__ out_len,
+                                                            uint32_t* __restrict__ status, uint32_t* next_item)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage_mem[kK2StageBytes];   // one window's output (K2's stage)
+    lds_bytes_t stage = (lds_bytes_t)stage_mem;
+    const uint32_t lane = threadIdx.x;
+
+    for (;;) {
+        uint32_t drawn = 0;
+        if (lane == 0) drawn = atomicAdd(next_item, 1u);
+        const uint32_t i = uni(drawn);
+        if (i >= count) break;
+        const uint8_t* src = load_global_ptr(&items[i].src);
+        uint8_t* dst = load_global_ptr(&items[i].dst);
+        const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));
+        const uint64_t capacity = dst ? uld64(reinterpret_cast<const uint8_t*>(&items[i].dst_capacity)) : 0;
+        // the header: a varint32 as Google's decoder reads it -- at most 5 bytes, the fifth below 16, inside the stream
+        uint32_t length = 0, hdr = 0;
+        if (src)
+            for (uint32_t k = 0; k < 5 && k < src_len; ++k) {
+                const uint32_t c = uni((uint32_t)src[k]);
+                if (k == 4 && c >= 16u) break;
+                length |= (c & 0x7fu) << (7u * k);
+                if (c < 0x80u) {
+                    hdr = k + 1;
+                    break;
+                }
+            }
+        uint32_t st;
+        if (hdr == 0) {
+            st = kBlockInvalid;
+            length = 0;
+        } else if (src_len > kRawMaxLen || length > kRawMaxLen) {
+            st = kRawTooLarge;
+        } else if (length > capacity) {
+            st = kRawDstTooSmall;
+        } else if (length == 0) {
+            st = src_len == hdr ? kBlockOk : kBlockInvalid;          // nothing may follow the header
+        } else {
+            st = k2_decode_block<true>(src, src_len, hdr, dst, length, stage);
+        }
+        if (lane == 0) {
+            status[i] = st;
+            out_len[i] = length;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- compress ----
+// words of the control line at the start of the scratch
+enum : uint32_t { kRawCtlFragments = 0 };    // fragments to compress: those of the items in front of the first one beyond max_fragments
+
+// Scratch of one call, every part rounded up to 256 bytes: control line, prefix[count + 1] (u64: first fragment of item i;
+// [count] = all fragments), frag_bytes[max_fragments] (u32: 4 + payload, as K1 leaves it), place[max_fragments] (u64: the
+// payload's offset in its item's dst), max_fragments compressed slots.
+struct RawLayout {
+    uint64_t prefix, frag_bytes, place, slots, total;
+};
+__host__ __device__ inline RawLayout raw_layout(uint32_t count, uint32_t max_fragments, uint32_t slot_stride)
+{
+    RawLayout l;
+    l.prefix = 256;
+    l.frag_bytes = l.prefix + update_round256(((uint64_t)count + 1u) * 8u);
+    l.place = l.frag_bytes + update_round256((uint64_t)max_fragments * 4u);
+    l.slots = l.place + update_round256((uint64_t)max_fragments * 8u);
+    l.total = l.slots + update_round256((uint64_t)max_fragments * slot_stride);
+    return l;
+}
+
+__device__ __forceinline__ uint32_t raw_varint_len(uint32_t v)
+{
+    uint32_t n = 1;
+    while (v >= 0x80u) { v >>= 7; ++n; }
+    return n;
+}
+
+// the item of fragment f: the last i with prefix[i] <= f (items of no fragments share their prefix with the next one)
+__device__ __forceinline__ uint32_t raw_item_of(const uint64_t* __restrict__ prefix, uint32_t count, uint32_t f)
+{
+    uint32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (prefix[mid] <= f) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(1024) void raw_plan_kernel(const RawItem* __restrict__ items, uint32_t count, uint32_t block_size,
+                                                        uint32_t max_fragments, uint64_t* __restrict__ out_len, uint32_t* __restrict__ status,
+                                                        uint32_t* __restrict__ result, uint32_t* __restrict__ ctl, uint64_t* __restrict__ prefix)
+{
+    __shared__ uint64_t wave_sums[16];
+    __shared__ uint64_t cut_s;
+    const uint32_t tid = threadIdx.x;
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < count; base += 1024) {
+        const uint32_t i = base + tid;
+        uint64_t mine = 0;
+        uint32_t st = kBlockOk;
+        if (i < count) {
+            const RawItem q = items[i];
+            if (q.src_len >> 32) st = kRawTooLarge;
+            else if (q.src_len && !q.src) st = kBlockInvalid;
+            else mine = (q.src_len + block_size - 1) / block_size;
+        }
+        uint64_t total;
+        const uint64_t first = carry + update_scan1024(mine, wave_sums, total);
+        if (i < count) {
+            prefix[i] = first;
+            // past max_fragments: the item that straddles it (exactly one when there are more fragments) marks the cut
+            const bool beyond = mine && first + mine > max_fragments;
+            if (beyond && first <= max_fragments) cut_s = first;
+            status[i] = beyond ? kRawTooLarge : st;
+            out_len[i] = 0;
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        prefix[count] = carry;
+        ctl[kRawCtlFragments] = (uint32_t)(carry > max_fragments ? cut_s : carry);
+        result[0] = carry > 0xffffffffull ? 0xffffffffu : (uint32_t)carry;
+        result[1] = 0;
+    }
+}
+
+// kForm: the form of K1's parse the LDS-table kernel of the product runs at this block size (3 = stream, 2 = bulk); launched
+// with that kernel's dynamic LDS (lds_table_stream_lds_bytes / lds_table_kernel_lds_bytes)
+template <int kForm>
+__global__ __launch_bounds__(64) void raw_compress_fragments_kernel(const RawItem* __restrict__ items, uint32_t count, uint32_t block_size,
+                                                                    const uint32_t* __restrict__ ctl, const uint64_t* __restrict__ prefix,
+                                                                    uint32_t* __restrict__ frag_bytes, uint8_t* __restrict__ slots,
+                                                                    uint32_t slot_stride, uint32_t* next_fragment)
+{
+    static_assert(kForm == 2 || kForm == 3, "the bulk (2) and the stream (3) form of the parse");
+    HIP_DYNAMIC_SHARED(uint8_t, lds_dyn)
+    uint16_t* table = reinterpret_cast<uint16_t*>(lds_dyn);
+    uint8_t* dup_scratch = lds_dyn + 2u * lds_table_entries(block_size);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t fragments = uni(ctl[kRawCtlFragments]);
+
+    for (;;) {
+        uint32_t drawn = 0;
+        if (lane == 0) drawn = atomicAdd(next_fragment, 1u);
+        const uint32_t f = uni(drawn);
+        if (f >= fragments) break;
+        const uint32_t i = raw_item_of(prefix, count, f);
+        const uint8_t* src = load_global_ptr(&items[i].src);
+        const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));   // (validated: < 4 GiB)
+        const uint64_t start = (f - uld64(reinterpret_cast<const uint8_t*>(prefix + i))) * block_size;
+        const uint64_t left = src_len - start;
+        const uint32_t n = left < block_size ? (uint32_t)left : block_size;
+        uint8_t* out = slots + (uint64_t)f * slot_stride;
+        if constexpr (kForm == 3) {
+            SoloMate solo;
+            compress_one_block_stream<LdsTable, kStreamSlotsLds>(src, start, src_len, n, out, LdsTable{table}, lane, frag_bytes + f,
+                                                                 (lds_bytes_t)dup_scratch, solo);
+        } else {
+            compress_one_block_bulk<LdsTable, 64>(src, start, src_len, n, out, LdsTable{table}, lane, frag_bytes + f, (lds_bytes_t)dup_scratch);
+        }
+        __syncthreads();
+    }
+}
+
+// One wavefront per item the plan left OK: the sizes of its fragments' payloads are scanned into their places behind the
+// header; an item that does not fit its dst is told the size it needs and keeps every byte of dst.
+__global__ __launch_bounds__(64) void raw_sizes_kernel(const RawItem* __restrict__ items, uint32_t count, const uint64_t* __restrict__ prefix,
+                                                       const uint32_t* __restrict__ frag_bytes, uint64_t* __restrict__ place,
+                                                       uint64_t* __restrict__ out_len, uint32_t* __restrict__ status, uint32_t* __restrict__ result)
+{
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        if (uni(status[i]) != kBlockOk) continue;
+        const uint64_t first = uld64(reinterpret_cast<const uint8_t*>(prefix + i)), end = uld64(reinterpret_cast<const uint8_t*>(prefix + i + 1));
+        const uint32_t src_len = (uint32_t)uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));
+        const uint32_t hdr = raw_varint_len(src_len);
+        uint64_t at = hdr;
+        for (uint64_t base = first; base < end; base += kWave) {
+            const uint64_t f = base + lane;
+            const uint32_t mine = f < end ? frag_bytes[f] - 4u : 0u;
+            uint32_t x = mine;
+            for (uint32_t d = 1; d < kWave; d <<= 1) {
+                const uint32_t t = (uint32_t)__shfl_up((int)x, (int)d);
+                if (lane >= d) x += t;
+            }
+            if (f < end) place[f] = at + (x - mine);
+            at += (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+        }
+        uint8_t* dst = load_global_ptr(&items[i].dst);
+        const uint64_t capacity = dst ? uld64(reinterpret_cast<const uint8_t*>(&items[i].dst_capacity)) : 0;
+        if (lane == 0) {
+            out_len[i] = at;
+            if (at > capacity) {
+                status[i] = kRawDstTooSmall;
+            } else {
+                uint32_t v = src_len, k = 0;
+                while (v >= 0x80u) { dst[k++] = (uint8_t)(v | 0x80u); v >>= 7; }
+                dst[k] = (uint8_t)v;
+                atomicAdd(result + 1, 1u);
+            }
+        }
+    }
+}
+
+// One 256-thread workgroup per fragment: frag_bytes[f] - 4 bytes from behind the size word of slot f to the fragment's place
+// in its item's dst; both ends at any alignment.  16-byte stores on the aligned middle of the destination (merge_stream_kernel).
+__global__ __launch_bounds__(256) void raw_gather_kernel(const RawItem* __restrict__ items, uint32_t count, const uint32_t* __restrict__ ctl,
+                                                         const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ frag_bytes,
+                                                         const uint64_t* __restrict__ place, const uint8_t* __restrict__ slots,
+                                                         uint32_t slot_stride, const uint32_t* __restrict__ status)
+{
+    const uint32_t fragments = ctl[kRawCtlFragments];
+    for (uint32_t f = blockIdx.x; f < fragments; f += gridDim.x) {
+        const uint32_t i = raw_item_of(prefix, count, f);
+        if (status[i] != kBlockOk) continue;
+        const uint8_t* src = slots + (uint64_t)f * slot_stride + 4;
+        uint8_t* dst = load_global_ptr(&items[i].dst) + place[f];
+        const uint32_t len = frag_bytes[f] - 4u;
+        const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);   // bytes until dst is 16-byte aligned
+        const uint32_t h = head < len ? head : len;
+        if (threadIdx.x < h) dst[threadIdx.x] = src[threadIdx.x];
+        const uint32_t body = (len - h) & ~15u;
+        for (uint32_t k = threadIdx.x * 16; k < body; k += 256 * 16)
+            *reinterpret_cast<uint4*>(dst + h + k) = ld128(src + h + k);
+        const uint32_t done = h + body;
+        if (done + threadIdx.x < len) dst[done + threadIdx.x] = src[done + threadIdx.x];
+    }
+}
+
+}  // namespace snappy_hip

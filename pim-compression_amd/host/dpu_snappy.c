@@ -5,7 +5,7 @@
  * snappy_decompress_dpu (dpu_snappy.c:169-172, :189-192).  Without -d the host CPU codec runs,
  * as in the reference.  -d never falls back to the CPU.
  *
- *   dpu_snappy [-d] [-c] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]
  */
 #include <getopt.h>
 #include <limits.h>
@@ -22,9 +22,10 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "**DEBUG BUILD**\n");
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
-	fprintf(stderr, "usage: %s [-d] [-c] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
+	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
 	fprintf(stderr, "r: decompress only <length> bytes from uncompressed byte <offset> of the input\n");
@@ -100,7 +101,8 @@ int main(int argc, char **argv)
 	int use_write = 0;
 	unsigned long long write_off = 0;
 	const char *patch_path = NULL;
-	while ((opt = getopt(argc, argv, "dcb:g:i:o:r:w:")) != -1) {
+	int raw = 0;
+	while ((opt = getopt(argc, argv, "dcRb:g:i:o:r:w:")) != -1) {
 		switch (opt) {
 		case 'w': {                  /* overwrite the uncompressed bytes from offset with the patch file's */
 			char *colon = NULL;
@@ -130,6 +132,7 @@ int main(int argc, char **argv)
 		}
 		case 'd': use_gpu = 1; break;
 		case 'c': compress = 1; break;
+		case 'R': raw = 1; break;
 		case 'b': block_size = atoi(optarg); break;
 		case 'g': setenv("SNAPPY_HIP_NUM_GPUS", optarg, 1); break;
 		case 'i': in_path = optarg; break;
@@ -149,6 +152,10 @@ int main(int argc, char **argv)
 	}
 	if (use_write && (compress || use_range)) {
 		fprintf(stderr, "-w overwrites bytes of a compressed file: it does not go with -c or -r\n");
+		return -2;
+	}
+	if (raw && (use_range || use_write)) {
+		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
 		return -2;
 	}
 	if (use_gpu) {
@@ -175,7 +182,25 @@ int main(int argc, char **argv)
 	memset(&rt, 0, sizeof(rt));                              /* the reference leaves this uninitialised */
 	snappy_status st;
 	struct timeval t0, t1;
-	if (compress) {
+	if (raw) {
+		/* one raw Snappy stream, either way; in -d mode one item through the batch calls of the library, which allocates
+		 * the output */
+		if (use_gpu) {
+			output.buffer = NULL;
+			output.curr = NULL;
+			output.max = ULONG_MAX;
+			st = compress ? snappy_compress_raw_gpu(&input, &output, (uint32_t)block_size, &rt) : snappy_decompress_raw_gpu(&input, &output, &rt);
+		} else {
+			if (compress)
+				setup_compression(&input, &output, &rt);
+			else if (setup_decompression(&input, &output, &rt))
+				return -1;
+			gettimeofday(&t0, NULL);
+			st = compress ? snappy_compress_raw_host(&input, &output, (uint32_t)block_size) : snappy_decompress_raw_host(&input, &output);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+	} else if (compress) {
 		if (use_gpu && g_pinned && block_size >= 1 && block_size <= 65535) {
 			/* page-locked output of the stream's upper bound; max = capacity tells the library not to realloc */
 			struct timeval a, b;

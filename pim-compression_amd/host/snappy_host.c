@@ -298,6 +298,51 @@ snappy_status snappy_decompress_host(struct host_buffer_context *input, struct h
 	return (op == out_end) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
 }
 
+/* ---- the raw format (dpu_snappy -R) ---------------------------------------- */
+
+/* varint(length), then the elements of every block_size fragment as host_compress_block writes them, less the size word:
+ * fragments never refer to each other, so their concatenation is one valid raw stream. */
+snappy_status snappy_compress_raw_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t block_size)
+{
+	if (block_size < 64 || block_size > 65535 || input->length > 0xffffffffUL)
+		return SNAPPY_INVALID_INPUT;
+	uint16_t *tab = malloc(TABLE_MAX * sizeof(*tab));
+	struct sink s = { output->buffer };
+	s.p = varint_put(s.p, (uint32_t)input->length);
+	const uint8_t *in = input->buffer;
+	unsigned long left = input->length;
+	while (left) {
+		uint32_t n = left < block_size ? (uint32_t)left : block_size;
+		uint8_t *const size_at = s.p;
+		host_compress_block(in, n, &s, tab);
+		s.p -= 4;
+		memmove(size_at, size_at + 4, (size_t)(s.p - size_at));
+		in += n;
+		left -= n;
+	}
+	free(tab);
+	input->curr = input->buffer + input->length;
+	output->curr = s.p;
+	output->length = (unsigned long)(s.p - output->buffer);
+	return SNAPPY_OK;
+}
+
+/* The whole file behind its header is ONE "block": decompress_block_host's lengths, offsets and bounds are as wide as the
+ * file.  The header is a varint32 as Google's decoder reads it: the fifth byte, if there is one, below 16. */
+snappy_status snappy_decompress_raw_host(struct host_buffer_context *input, struct host_buffer_context *output)
+{
+	if (input->curr - input->buffer == 5 && input->curr[-1] >= 16)
+		return SNAPPY_INVALID_INPUT;
+	uint8_t *const out0 = output->buffer;
+	uint8_t *const out_end = out0 + output->length;
+	uint8_t *op = decompress_block_host(input->curr, input->buffer + input->length, out0, out0, out_end);
+	if (!op)
+		return SNAPPY_INVALID_INPUT;
+	input->curr = input->buffer + input->length;
+	output->curr = op;
+	return (op == out_end) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
+}
+
 /* Bytes [offset, offset + length) of a whole framed file (input->buffer at its first byte): the size chain walked up to the
  * last block the range touches, only the touched blocks decoded.  output->buffer is malloc'd here (length bytes). */
 snappy_status snappy_decompress_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,

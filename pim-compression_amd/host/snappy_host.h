@@ -23,6 +23,11 @@ snappy_status snappy_decompress_range_host(struct host_buffer_context *input, st
 /* dpu_snappy -w: patch over plaintext bytes [offset, offset + patch->length), recompressing only the blocks it touches */
 snappy_status snappy_update_range_host(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
                                        struct host_buffer_context *output);
+/* dpu_snappy -R: the original ("raw") Snappy format, varint(length) + one element stream.  Compression writes the elements of
+ * the input's block_size fragments without their size words (output from setup_compression); decompression (output from
+ * setup_decompression, input->curr behind the header) takes streams of any compressor. */
+snappy_status snappy_compress_raw_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t block_size);
+snappy_status snappy_decompress_raw_host(struct host_buffer_context *input, struct host_buffer_context *output);
 double get_runtime(struct timeval *start, struct timeval *end);
 
 #ifdef __cplusplus

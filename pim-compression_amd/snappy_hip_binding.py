@@ -101,9 +101,23 @@ def lib():
         L.snappy_hip_update_scratch_bytes.argtypes = [u32, u32, u32, u32]
         L.snappy_hip_update_ranges.restype = ctypes.c_int
         L.snappy_hip_update_ranges.argtypes = [vp, u32, u32, vp, u32, vp, vp, u64, vp, vp, vp, u32, vp, u64, vp]
+        L.snappy_hip_raw_decompress_batch.restype = ctypes.c_int
+        L.snappy_hip_raw_decompress_batch.argtypes = [vp, u32, vp, vp, vp]
+        L.snappy_hip_raw_compress_bound.restype = u64
+        L.snappy_hip_raw_compress_bound.argtypes = [u64, u32]
+        L.snappy_hip_raw_compress_scratch_bytes.restype = u64
+        L.snappy_hip_raw_compress_scratch_bytes.argtypes = [u32, u32, u32]
+        L.snappy_hip_raw_compress_batch.restype = ctypes.c_int
+        L.snappy_hip_raw_compress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp]
         L.snappy_update_range_gpu.restype = ctypes.c_int
         L.snappy_update_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64,
                                               ctypes.POINTER(HostBufferContext), ctypes.POINTER(ProgramRuntime)]
+        L.snappy_compress_raw_gpu.restype = ctypes.c_int
+        L.snappy_compress_raw_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                              ctypes.POINTER(ProgramRuntime)]
+        L.snappy_decompress_raw_gpu.restype = ctypes.c_int
+        L.snappy_decompress_raw_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext),
+                                                ctypes.POINTER(ProgramRuntime)]
         L.snappy_compress_gpu.restype = ctypes.c_int
         L.snappy_compress_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
                                           ctypes.POINTER(ProgramRuntime)]
@@ -397,6 +411,55 @@ def update_ranges(d_desc, total_len, block_size, d_writes, write_count, d_write_
     return d_scratch
 
 
+# batches of raw Snappy streams, described on the device (snappy_hip_raw_decompress_batch / snappy_hip_raw_compress_batch)
+RAW_DST_TOO_SMALL = 5
+RAW_TOO_LARGE = 6
+RAW_MAX_LEN = 0x7ffff000
+RAW_ITEM_DTYPE = np.dtype([("src", "<u8"), ("src_len", "<u8"), ("dst", "<u8"), ("dst_capacity", "<u8")])   # snappy_hip_raw_item
+
+
+def make_raw_items(entries, device="cuda"):
+    """entries: list of (src, src_len, dst, dst_capacity) with src and dst device addresses (int, 0 = null) -> device tensor of
+    snappy_hip_raw_item."""
+    import torch
+    arr = np.zeros(max(len(entries), 1), dtype=RAW_ITEM_DTYPE)
+    for i, e in enumerate(entries):
+        arr[i] = tuple(e)
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
+def raw_decompress_batch(d_items, count, d_out_len, d_status):
+    """Enqueue snappy_hip_raw_decompress_batch on the current stream.  d_items: make_raw_items() tensor or any device uint8
+    tensor of packed snappy_hip_raw_item, d_out_len: device int64 tensor and d_status: device int32 tensor of `count` entries.
+    Nothing is synchronised."""
+    import torch
+    _check(lib().snappy_hip_raw_decompress_batch(d_items.data_ptr(), count, d_out_len.data_ptr(), d_status.data_ptr(), _stream_handle(torch)),
+           "snappy_hip_raw_decompress_batch")
+
+
+def raw_compress_bound(src_len, block_size):
+    """A dst_capacity that always suffices for an item of src_len bytes (0 for a bad block size)."""
+    return int(lib().snappy_hip_raw_compress_bound(src_len, block_size))
+
+
+def raw_compress_scratch_bytes(block_size, count, max_fragments):
+    """Scratch of snappy_hip_raw_compress_batch (0 for a bad block size)."""
+    return int(lib().snappy_hip_raw_compress_scratch_bytes(block_size, count, max_fragments))
+
+
+def raw_compress_batch(d_items, count, block_size, max_fragments, d_out_len, d_status, d_result, d_scratch=None):
+    """Enqueue snappy_hip_raw_compress_batch on the current stream.  d_out_len: device int64 tensor and d_status: device int32
+    tensor of `count` entries, d_result: device int32 tensor of two.  d_scratch: 256-byte aligned device uint8 tensor (default: a
+    fresh one).  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(raw_compress_scratch_bytes(block_size, count, max_fragments), dtype=torch.uint8, device=d_result.device)
+    _check(lib().snappy_hip_raw_compress_batch(d_items.data_ptr(), count, block_size, max_fragments, d_out_len.data_ptr(),
+                                               d_status.data_ptr(), d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(),
+                                               _stream_handle(torch)), "snappy_hip_raw_compress_batch")
+    return d_scratch
+
+
 # ---------------------------------------------------------------------------
 # drop-in pair (host buffers), driven the way dpu_snappy.c's main() drives the *_dpu functions
 # ---------------------------------------------------------------------------
@@ -485,3 +548,29 @@ def update_range_host(stream, offset, data, out_capacity=None):
     if out.buffer:
         libc().free(out.buffer)
     return st, new, rt.as_dict()
+
+
+def _raw_host(call, data, out_capacity):
+    a = np.frombuffer(data, dtype=np.uint8).copy() if len(data) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(data), (1 << 64) - 1)
+    if out_capacity is None:
+        out = HostBufferContext(b"<memory>", None, None, 0, (1 << 64) - 1)
+    else:
+        buf = libc().malloc(max(1, out_capacity))
+        out = HostBufferContext(b"<memory>", buf, buf, 0, out_capacity)
+    rt = ProgramRuntime()
+    st = call(ctypes.byref(inp), ctypes.byref(out), ctypes.byref(rt))
+    got = ctypes.string_at(out.buffer, out.length) if st == SNAPPY_OK else b""
+    if out.buffer:
+        libc().free(out.buffer)
+    return st, got, rt.as_dict()
+
+
+def raw_compress_host(data, block_size=32768, out_capacity=None):
+    """snappy_compress_raw_gpu on a host buffer -> (status, raw Snappy stream, runtime dict).  out_capacity: as in compress_host."""
+    return _raw_host(lambda i, o, r: lib().snappy_compress_raw_gpu(i, o, block_size, r), data, out_capacity)
+
+
+def raw_decompress_host(stream, out_capacity=None):
+    """snappy_decompress_raw_gpu on a whole raw Snappy stream held in host memory -> (status, plaintext, runtime dict)."""
+    return _raw_host(lambda i, o, r: lib().snappy_decompress_raw_gpu(i, o, r), stream, out_capacity)
