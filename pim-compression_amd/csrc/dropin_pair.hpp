@@ -164,6 +164,27 @@ struct ShardCleanup {
     }
 };
 
+// zeroed by every call; `pre` accumulates over a program's calls (dpu_snappy.c:169-192)
+void zero_phases(struct program_runtime* rt) { rt->d_alloc = rt->load = rt->copy_in = rt->run = rt->copy_out = rt->d_free = 0.0; }
+
+snappy_status say(const dropin_plan::Verdict& v)
+{
+    fprintf(stderr, "%s\n", v.message.c_str());
+    return v.status;
+}
+
+snappy_status no_device()
+{
+    fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
+    return SNAPPY_INVALID_INPUT;
+}
+
+void place(struct host_buffer_context* output, uint64_t n)
+{
+    output->length = n;
+    output->curr = output->buffer + n;
+}
+
 snappy_status report(const char* where)
 {
     fprintf(stderr, "snappy_hip: %s failed: %s\n", where, g_last_error.c_str());
@@ -266,11 +287,8 @@ snappy_status compress_gpu_body(struct host_buffer_context* input, struct host_b
     double t0 = now_seconds();
     if (!input || !output || !runtime) return SNAPPY_INVALID_INPUT;
     if (input->length && !input->buffer) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
-    if (!block_size_ok(block_size)) {
-        fprintf(stderr, "snappy_hip: block size %u is outside 1..65535 (16-bit hash table entries)\n", block_size);
-        return SNAPPY_INVALID_INPUT;
-    }
+    zero_phases(runtime);
+    if (!block_size_ok(block_size)) return say(dropin_plan::bad_block_size(block_size, ""));
     if (input->length > 0xffffffffull) {
         fprintf(stderr, "snappy_hip: input of %lu bytes does not fit the format's uint32 length\n", input->length);
         return SNAPPY_BUFFER_TOO_SMALL;
@@ -278,10 +296,7 @@ snappy_status compress_gpu_body(struct host_buffer_context* input, struct host_b
     const uint64_t n = input->length;
     const uint64_t nb = snappy_hip_num_blocks(n, block_size);
     const ShardDevices devs = requested_devices();
-    if (devs.shards <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
+    if (devs.shards <= 0) return no_device();
     const int gpus = dropin_plan::shard_count(devs.shards, nb);
     const std::vector<dropin_plan::Range> part = dropin_plan::partition(nb, gpus, n, block_size);
     std::vector<CompressShard> sh(part.begin(), part.end());
@@ -462,8 +477,7 @@ snappy_status compress_gpu_body(struct host_buffer_context* input, struct host_b
         uint8_t* nbuf = (uint8_t*)realloc(output->buffer, total ? total : 1);
         if (nbuf) output->buffer = nbuf;
     }
-    output->length = total;
-    output->curr = output->buffer + total;
+    place(output, total);
     return SNAPPY_OK;
 }
 
@@ -474,7 +488,7 @@ snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host
     double t0 = now_seconds();
     if (!input || !output || !runtime) return SNAPPY_INVALID_INPUT;
     if (!input->buffer || !input->curr || input->curr < input->buffer) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+    zero_phases(runtime);
 
     // block-size varint (snappy_decompress.c:298-303)
     const uint8_t* const buf = input->buffer;
@@ -493,10 +507,7 @@ snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host
         runtime->pre += now_seconds() - t0;
         return (at == in_total) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
     }
-    if (!block_size_ok(bs)) {
-        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
-        return SNAPPY_INVALID_INPUT;
-    }
+    if (!block_size_ok(bs)) return say(dropin_plan::bad_block_size(bs, " in the stream"));
     if (!output->buffer) {
         fprintf(stderr, "snappy_hip: output->buffer is NULL (setup_decompression allocates it, snappy_decompress.c:207-209)\n");
         return SNAPPY_INVALID_INPUT;
@@ -510,10 +521,7 @@ snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host
         return SNAPPY_INVALID_INPUT;
     }
     const ShardDevices devs = requested_devices();
-    if (devs.shards <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
+    if (devs.shards <= 0) return no_device();
     const int gpus = dropin_plan::shard_count(devs.shards, nb);
     const uint64_t per = dropin_plan::shard_blocks(nb, gpus);
     const dropin_plan::DecompressChunking plan = dropin_plan::decompress_chunking(
@@ -641,279 +649,10 @@ snappy_status decompress_gpu_body(struct host_buffer_context* input, struct host
     return SNAPPY_OK;
 }
 
-// One byte range of a framed file (snappy_decompress_range_gpu): the header, the size chain on the host up to the last block
-// the range touches, only those blocks' bytes to the device, one range through snappy_hip_decompress_ranges on the current
-// device, `length` bytes back.  Phased and synchronous, as the reference's own steps (snappy_decompress.c:292-493).
-struct DeviceBuffers {
-    std::vector<void*> mem;
-    ~DeviceBuffers()
-    {
-        for (void* p : mem) (void)hipFree(p);
-    }
-    int alloc(void** p, size_t n)
-    {
-        HIP_TRY(hipMalloc(p, n ? n : 1));
-        mem.push_back(*p);
-        return 0;
-    }
-};
+// ---- The single-device calls (byte-range decode, byte-range overwrite, raw Snappy): no sharding, no overlap. ----
 
-snappy_status decompress_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint64_t offset,
-                                        uint64_t length, struct program_runtime* runtime)
-{
-    double t0 = now_seconds();
-    if (!input || !output || !runtime || !input->buffer) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
-    const uint8_t* const buf = input->buffer;
-    const uint64_t in_total = input->length;
-    uint32_t total = 0, bs = 0;
-    const uint32_t hdr = snappy_hip_parse_header(buf, in_total, &total, &bs);   // snappy_decompress.c:193-198, :298-303
-    if (!hdr) {
-        fprintf(stderr, "Failed to read the stream header\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (offset + length < offset || offset + length > total) {
-        fprintf(stderr, "snappy_hip: range %lu:%lu lies beyond the %u uncompressed bytes\n", (unsigned long)offset, (unsigned long)length, total);
-        return SNAPPY_INVALID_INPUT;
-    }
-    // the output buffer: the caller's (finite max) or ours (snappy_compress_gpu's rule)
-    const bool caller_owned = output->buffer && output->max != ~0UL;
-    if (caller_owned && output->max < length) {
-        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the %lu-byte range\n", (unsigned long)output->max,
-                (unsigned long)length);
-        return SNAPPY_BUFFER_TOO_SMALL;
-    }
-    if (!caller_owned) {
-        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, length ? length : 1);
-        if (!nbuf) {
-            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)length);
-            return SNAPPY_BUFFER_TOO_SMALL;
-        }
-        output->buffer = nbuf;
-    }
-    output->length = 0;
-    output->curr = output->buffer;
-    if (length == 0) {
-        runtime->pre += now_seconds() - t0;
-        return SNAPPY_OK;
-    }
-    if (!block_size_ok(bs)) {
-        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
-        return SNAPPY_INVALID_INPUT;
-    }
-    const uint64_t first = offset / bs, last = (offset + length - 1) / bs;
-    if (last + 1 > (in_total - hdr) / 4) {       // every block needs its u32 size prefix: checked before anything is sized by it
-        fprintf(stderr, "snappy_hip: truncated stream (block %lu)\n", (unsigned long)last);
-        return SNAPPY_INVALID_INPUT;
-    }
-    // the chain up to the last touched block (:317-340); offsets relative to the first touched block's
-    std::vector<uint64_t> off(last + 2, 0);
-    const dropin_plan::Walk w = dropin_plan::walk_chain(buf, in_total, 0, off.data(), {0, hdr}, last + 1);
-    if (w.stop != dropin_plan::kDone) {
-        fprintf(stderr, "snappy_hip: truncated stream (block %lu)\n", (unsigned long)(w.stop == dropin_plan::kLeaves ? w.block + 1 : w.block));
-        return SNAPPY_INVALID_INPUT;
-    }
-    const uint64_t in_lo = off[first], in_len = off[last + 1] - in_lo;
-    for (uint64_t b = 0; b <= last; ++b) off[b] = b >= first ? off[b] - in_lo : 0;
-    if (snappy_hip_device_count() <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    const uint64_t pieces = last - first + 1;
-    const uint64_t scratch_bytes = snappy_hip::range_prefix_bytes(1) + std::min<uint64_t>(pieces, range_grid_cap()) * snappy_hip::range_slot_bytes(bs);
-    runtime->pre += now_seconds() - t0;
-
-    DeviceBuffers dev;
-    uint8_t *d_stream = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    uint64_t* d_boff = nullptr;
-    snappy_hip_stream_desc* d_desc = nullptr;
-    snappy_hip_range* d_range = nullptr;
-    uint32_t* d_status = nullptr;
-    double t = now_seconds();
-    if (dev.alloc((void**)&d_stream, in_len) || dev.alloc((void**)&d_boff, (last + 1) * sizeof(uint64_t)) ||
-        dev.alloc((void**)&d_desc, sizeof(snappy_hip_stream_desc)) || dev.alloc((void**)&d_range, sizeof(snappy_hip_range)) ||
-        dev.alloc((void**)&d_status, sizeof(uint32_t)) || dev.alloc((void**)&d_out, length) || dev.alloc((void**)&d_scratch, scratch_bytes))
-        return report("device allocation");
-    runtime->d_alloc = now_seconds() - t;
-    t = now_seconds();
-    if (warm_up_device()) return report("code object load");
-    runtime->load = now_seconds() - t;
-    // copy in: the touched blocks, their offsets and the one descriptor + range
-    snappy_hip_stream_desc desc{d_stream, in_len, d_boff, nullptr, total, bs, hdr, (uint32_t)(last + 1)};
-    snappy_hip_range range{offset, length, d_out, 0, 0};
-    t = now_seconds();
-    if (hipMemcpy(d_stream, buf + in_lo, in_len, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_boff, off.data(), (last + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_desc, &desc, sizeof desc, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_range, &range, sizeof range, hipMemcpyHostToDevice) != hipSuccess) {
-        g_last_error = "hipMemcpy to the device";
-        return report("host-to-device copy");
-    }
-    runtime->copy_in = now_seconds() - t;
-    t = now_seconds();
-    if (snappy_hip_decompress_ranges(d_desc, 1, d_range, 1, d_status, bs, d_scratch, scratch_bytes, nullptr) != SNAPPY_HIP_OK)
-        return report("range decode launch");
-    if (hipDeviceSynchronize() != hipSuccess) {
-        g_last_error = "hipDeviceSynchronize after the range decode";
-        return report("range decode");
-    }
-    runtime->run = now_seconds() - t;
-    t = now_seconds();
-    uint32_t status = 0xffffffffu;
-    if (hipMemcpy(&status, d_status, sizeof status, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(output->buffer, d_out, length, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_last_error = "hipMemcpy to the host";
-        return report("device-to-host copy");
-    }
-    runtime->copy_out = now_seconds() - t;
-    t = now_seconds();
-    for (void* p : dev.mem) (void)hipFree(p);
-    dev.mem.clear();
-    runtime->d_free = now_seconds() - t;
-    if (status != SNAPPY_HIP_BLOCK_OK) {
-        fprintf(stderr, "snappy_hip: a block of the range [%lu, %lu) does not decode (status %u)\n", (unsigned long)offset,
-                (unsigned long)(offset + length), status);
-        return SNAPPY_INVALID_INPUT;
-    }
-    output->length = length;
-    output->curr = output->buffer + length;
-    return SNAPPY_OK;
-}
-
-// One overwrite of a framed file (snappy_update_range_gpu): the header and the whole size chain on the host, the whole stream
-// to the current device, one write through snappy_hip_update_ranges, the new stream back.  Phased and synchronous.
-snappy_status update_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* patch, uint64_t offset,
-                                    struct host_buffer_context* output, struct program_runtime* runtime)
-{
-    double t0 = now_seconds();
-    if (!input || !patch || !output || !runtime || !input->buffer || (patch->length && !patch->buffer)) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
-    const uint8_t* const buf = input->buffer;
-    const uint64_t in_total = input->length, length = patch->length;
-    uint32_t total = 0, bs = 0;
-    const uint32_t hdr = snappy_hip_parse_header(buf, in_total, &total, &bs);
-    if (!hdr) {
-        fprintf(stderr, "Failed to read the stream header\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (offset + length < offset || offset + length > total) {
-        fprintf(stderr, "snappy_hip: write %lu:%lu lies beyond the %u uncompressed bytes\n", (unsigned long)offset, (unsigned long)length, total);
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (total && !block_size_ok(bs)) {
-        fprintf(stderr, "snappy_hip: block size %u in the stream is outside 1..65535\n", bs);
-        return SNAPPY_INVALID_INPUT;
-    }
-    const uint64_t nb = total ? snappy_hip_num_blocks(total, bs) : 0;
-    if (nb > (in_total - hdr) / 4) {             // every block needs its u32 size prefix: checked before anything is sized by it
-        fprintf(stderr, "snappy_hip: truncated stream (%lu blocks)\n", (unsigned long)nb);
-        return SNAPPY_INVALID_INPUT;
-    }
-    std::vector<uint64_t> off(nb + 1, hdr);
-    if (nb) {
-        const dropin_plan::Walk w = dropin_plan::walk_chain(buf, in_total, 0, off.data(), {0, hdr}, nb);
-        if (w.stop != dropin_plan::kDone) {
-            fprintf(stderr, "snappy_hip: truncated stream (block %lu)\n", (unsigned long)(w.stop == dropin_plan::kLeaves ? w.block + 1 : w.block));
-            return SNAPPY_INVALID_INPUT;
-        }
-    }
-    if (off[nb] != in_total) {
-        fprintf(stderr, "snappy_hip: %lu bytes behind the last block\n", (unsigned long)(in_total - off[nb]));
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (snappy_hip_device_count() <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    const uint32_t dirty_max = length ? (uint32_t)((offset + length - 1) / bs - offset / bs + 1) : 0;
-    const uint32_t bs_arg = total ? bs : 32768u;          // (an empty container's block size may be anything: nothing is sized by it)
-    // a dirty block grows to a slot at most, a clean one keeps its size
-    const uint64_t capacity = in_total + (uint64_t)dirty_max * snappy_hip_slot_stride(bs_arg) + 16;
-    const uint64_t scratch_bytes = snappy_hip_update_scratch_bytes(bs_arg, (uint32_t)nb, 1, std::max(1u, dirty_max));
-    runtime->pre += now_seconds() - t0;
-
-    DeviceBuffers dev;
-    uint8_t *d_stream = nullptr, *d_new = nullptr, *d_scratch = nullptr, *d_patch = nullptr;
-    uint64_t *d_boff = nullptr, *d_noff = nullptr;      // d_noff: the new offsets, then the new length
-    snappy_hip_stream_desc* d_desc = nullptr;
-    snappy_hip_write* d_write = nullptr;
-    uint32_t* d_words = nullptr;                        // [0] the write's status, [1..2] the result
-    double t = now_seconds();
-    if (dev.alloc((void**)&d_stream, in_total) || dev.alloc((void**)&d_boff, (nb + 1) * sizeof(uint64_t)) ||
-        dev.alloc((void**)&d_noff, (nb + 2) * sizeof(uint64_t)) || dev.alloc((void**)&d_desc, sizeof(snappy_hip_stream_desc)) ||
-        dev.alloc((void**)&d_write, sizeof(snappy_hip_write)) || dev.alloc((void**)&d_words, 4 * sizeof(uint32_t)) ||
-        dev.alloc((void**)&d_patch, length) || dev.alloc((void**)&d_new, capacity) || dev.alloc((void**)&d_scratch, scratch_bytes))
-        return report("device allocation");
-    runtime->d_alloc = now_seconds() - t;
-    t = now_seconds();
-    if (warm_up_device()) return report("code object load");
-    runtime->load = now_seconds() - t;
-    snappy_hip_stream_desc desc{d_stream, in_total, d_boff, nullptr, total, bs_arg, hdr, (uint32_t)nb};
-    snappy_hip_write write{offset, length, d_patch, 0};
-    t = now_seconds();
-    if (hipMemcpy(d_stream, buf, in_total, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_boff, off.data(), (nb + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_desc, &desc, sizeof desc, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_write, &write, sizeof write, hipMemcpyHostToDevice) != hipSuccess ||
-        (length && hipMemcpy(d_patch, patch->buffer, length, hipMemcpyHostToDevice) != hipSuccess)) {
-        g_last_error = "hipMemcpy to the device";
-        return report("host-to-device copy");
-    }
-    runtime->copy_in = now_seconds() - t;
-    t = now_seconds();
-    if (snappy_hip_update_ranges(d_desc, total, bs_arg, d_write, 1, d_words, d_new, capacity, d_noff, d_noff + nb + 1, d_words + 1,
-                                 std::max(1u, dirty_max), d_scratch, scratch_bytes, nullptr) != SNAPPY_HIP_OK)
-        return report("update launch");
-    if (hipDeviceSynchronize() != hipSuccess) {
-        g_last_error = "hipDeviceSynchronize after the update";
-        return report("update");
-    }
-    runtime->run = now_seconds() - t;
-    t = now_seconds();
-    uint32_t words[3] = {0xffffffffu, 0xffffffffu, 0};
-    uint64_t new_len = 0;
-    if (hipMemcpy(words, d_words, sizeof words, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&new_len, d_noff + nb + 1, sizeof new_len, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_last_error = "hipMemcpy to the host";
-        return report("device-to-host copy");
-    }
-    if (words[0] != SNAPPY_HIP_BLOCK_OK || words[1] != SNAPPY_HIP_BLOCK_OK || new_len > capacity) {
-        fprintf(stderr, "snappy_hip: the stream cannot be updated (write status %u, result %u)\n", words[0], words[1]);
-        return SNAPPY_INVALID_INPUT;
-    }
-    // the output buffer: the caller's (finite max) or ours (snappy_compress_gpu's rule)
-    const bool caller_owned = output->buffer && output->max != ~0UL;
-    if (caller_owned && output->max < new_len) {
-        fprintf(stderr, "snappy_hip: output buffer of %lu bytes cannot hold the %lu-byte stream\n", (unsigned long)output->max,
-                (unsigned long)new_len);
-        return SNAPPY_BUFFER_TOO_SMALL;
-    }
-    if (!caller_owned) {
-        uint8_t* nbuf = (uint8_t*)realloc(output->buffer, new_len ? new_len : 1);
-        if (!nbuf) {
-            fprintf(stderr, "snappy_hip: cannot allocate %lu bytes for the output\n", (unsigned long)new_len);
-            return SNAPPY_BUFFER_TOO_SMALL;
-        }
-        output->buffer = nbuf;
-    }
-    if (hipMemcpy(output->buffer, d_new, new_len, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_last_error = "hipMemcpy to the host";
-        return report("device-to-host copy");
-    }
-    runtime->copy_out = now_seconds() - t;
-    t = now_seconds();
-    for (void* p : dev.mem) (void)hipFree(p);
-    dev.mem.clear();
-    runtime->d_free = now_seconds() - t;
-    output->length = new_len;
-    output->curr = output->buffer + new_len;
-    return SNAPPY_OK;
-}
-
-// The raw ("original") Snappy format, one buffer each way on the current device: one item through the batch calls of
-// snappy_raw.hpp, no sharding.  Phased and synchronous like the range call above.
-// claims the output buffer for `n` bytes: the caller's (finite max) or ours (snappy_compress_gpu's rule)
-snappy_status raw_output_buffer(struct host_buffer_context* output, uint64_t n)
+// claims output->buffer for n bytes: the caller's where its max is finite, else (re)allocated here
+snappy_status claim_output(struct host_buffer_context* output, uint64_t n)
 {
     const bool caller_owned = output->buffer && output->max != ~0UL;
     if (caller_owned && output->max < n) {
@@ -931,6 +670,220 @@ snappy_status raw_output_buffer(struct host_buffer_context* output, uint64_t n)
     return SNAPPY_OK;
 }
 
+// One phased, synchronous call on the current device, in the reference's own steps (snappy_decompress.c:292-493): host checks
+// (`pre`), buffers, load, uploads, one launch, the way back, free -- each timed into its program_runtime field, a failed step
+// reported once.  Device memory goes back when the call leaves, however it leaves.
+struct PhasedCall {
+    struct Want {
+        void** p;
+        uint64_t bytes;
+        template <class T>
+        Want(T** p, uint64_t bytes) : p((void**)p), bytes(bytes) {}
+    };
+    struct Copy {
+        void* dst;
+        const void* src;
+        uint64_t bytes;
+    };
+
+    struct program_runtime* const rt;
+    const double t0 = now_seconds();
+    std::vector<void*> mem;
+
+    explicit PhasedCall(struct program_runtime* runtime) : rt(runtime) { zero_phases(rt); }
+    ~PhasedCall() { release(); }
+    void release()
+    {
+        for (void* p : mem) (void)hipFree(p);
+        mem.clear();
+    }
+
+    // fn's seconds go to *field, its failure (non-zero, g_last_error set) becomes report(where)
+    template <class Fn>
+    snappy_status phase(double* field, const char* where, Fn fn)
+    {
+        const double t = now_seconds();
+        if (fn()) return report(where);
+        *field = now_seconds() - t;
+        return SNAPPY_OK;
+    }
+
+    // a call that the host alone decides
+    snappy_status done_on_host()
+    {
+        rt->pre += now_seconds() - t0;
+        return SNAPPY_OK;
+    }
+    snappy_status need_device() const { return snappy_hip_device_count() > 0 ? SNAPPY_OK : no_device(); }
+
+    // the end of `pre`: the buffers (dpu_alloc), then the load phase
+    snappy_status buffers(std::initializer_list<Want> wants)
+    {
+        rt->pre += now_seconds() - t0;
+        const snappy_status st = phase(&rt->d_alloc, "device allocation", [&]() -> int {
+            for (const Want& w : wants) {
+                HIP_TRY(hipMalloc(w.p, w.bytes ? w.bytes : 1));
+                mem.push_back(*w.p);
+            }
+            return 0;
+        });
+        return st ? st : phase(&rt->load, "code object load", warm_up_device);
+    }
+
+    static int copy(std::initializer_list<Copy> copies, hipMemcpyKind kind, const char* what)
+    {
+        for (const Copy& c : copies)
+            if (c.bytes && hipMemcpy(c.dst, c.src, c.bytes, kind) != hipSuccess) return fail(SNAPPY_HIP_ERR_RUNTIME, what);
+        return 0;
+    }
+    snappy_status upload(std::initializer_list<Copy> copies)
+    {
+        return phase(&rt->copy_in, "host-to-device copy", [&] { return copy(copies, hipMemcpyHostToDevice, "hipMemcpy to the device"); });
+    }
+    // run = launch + synchronize
+    template <class Fn>
+    snappy_status launch(const char* what, Fn fn)
+    {
+        return phase(&rt->run, what, [&]() -> int {
+            if (int rc = fn()) return rc;
+            HIP_TRY(hipDeviceSynchronize());
+            return 0;
+        });
+    }
+    // copy_out = fn: download()s, with whatever the call decides between them (its verdict, its output buffer)
+    template <class Fn>
+    snappy_status copy_out(Fn fn)
+    {
+        return phase(&rt->copy_out, "device-to-host copy", fn);
+    }
+    static int download(std::initializer_list<Copy> copies) { return copy(copies, hipMemcpyDeviceToHost, "hipMemcpy to the host"); }
+    snappy_status free_buffers()
+    {
+        return phase(&rt->d_free, "free", [&] {
+            release();
+            return 0;
+        });
+    }
+};
+
+// One byte range of a framed file (snappy_decompress_range_gpu): the header, the size chain on the host up to the last block
+// the range touches, only those blocks' bytes to the device, one range through snappy_hip_decompress_ranges, `length` bytes back.
+snappy_status decompress_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint64_t offset,
+                                        uint64_t length, struct program_runtime* runtime)
+{
+    if (!input || !output || !runtime || !input->buffer) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length;
+    const dropin_plan::Container c = dropin_plan::open_container(buf, in_total);
+    dropin_plan::Span span;
+    if (const dropin_plan::Verdict v = dropin_plan::resolve_span(c, offset, length, "range", &span)) return say(v);
+    if (snappy_status st = claim_output(output, length)) return st;
+    place(output, 0);
+    if (length == 0) return call.done_on_host();
+    std::vector<uint64_t> off;      // (:317-340), then relative to the first touched block's
+    if (const dropin_plan::Verdict v = dropin_plan::walk_to(buf, in_total, c, span.last + 1, false, off)) return say(v);
+    const uint64_t in_lo = off[span.first], in_len = off[span.last + 1] - in_lo;
+    for (uint64_t b = 0; b <= span.last; ++b) off[b] = b >= span.first ? off[b] - in_lo : 0;
+    if (snappy_status st = call.need_device()) return st;
+    const uint64_t scratch_bytes =
+        snappy_hip::range_prefix_bytes(1) + std::min<uint64_t>(span.blocks, range_grid_cap()) * snappy_hip::range_slot_bytes(c.bs);
+
+    uint8_t *d_stream = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    uint64_t* d_boff = nullptr;
+    snappy_hip_stream_desc* d_desc = nullptr;
+    snappy_hip_range* d_range = nullptr;
+    uint32_t* d_status = nullptr;
+    if (snappy_status st = call.buffers({{&d_stream, in_len}, {&d_boff, (span.last + 1) * sizeof(uint64_t)}, {&d_desc, sizeof *d_desc},
+                                         {&d_range, sizeof *d_range}, {&d_status, sizeof *d_status}, {&d_out, length},
+                                         {&d_scratch, scratch_bytes}}))
+        return st;
+    const snappy_hip_stream_desc desc{d_stream, in_len, d_boff, nullptr, c.total, c.bs, c.hdr, (uint32_t)(span.last + 1)};
+    const snappy_hip_range range{offset, length, d_out, 0, 0};
+    if (snappy_status st = call.upload({{d_stream, buf + in_lo, in_len}, {d_boff, off.data(), (span.last + 1) * sizeof(uint64_t)},
+                                        {d_desc, &desc, sizeof desc}, {d_range, &range, sizeof range}}))
+        return st;
+    if (snappy_status st = call.launch("range decode", [&] {
+            return snappy_hip_decompress_ranges(d_desc, 1, d_range, 1, d_status, c.bs, d_scratch, scratch_bytes, nullptr);
+        }))
+        return st;
+    uint32_t status = 0xffffffffu;
+    if (snappy_status st = call.copy_out([&] {
+            return call.download({{&status, d_status, sizeof status}, {output->buffer, d_out, length}});
+        }))
+        return st;
+    if (snappy_status st = call.free_buffers()) return st;
+    if (status != SNAPPY_HIP_BLOCK_OK) {
+        fprintf(stderr, "snappy_hip: a block of the range [%lu, %lu) does not decode (status %u)\n", (unsigned long)offset,
+                (unsigned long)(offset + length), status);
+        return SNAPPY_INVALID_INPUT;
+    }
+    place(output, length);
+    return SNAPPY_OK;
+}
+
+// One overwrite of a framed file (snappy_update_range_gpu): the header and the whole size chain on the host, the whole stream
+// to the device, one write through snappy_hip_update_ranges, the new stream back.  `output` is left alone until it succeeds.
+snappy_status update_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* patch, uint64_t offset,
+                                    struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    if (!input || !patch || !output || !runtime || !input->buffer || (patch->length && !patch->buffer)) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length, length = patch->length;
+    const dropin_plan::Container c = dropin_plan::open_container(buf, in_total);
+    dropin_plan::Span span;
+    if (const dropin_plan::Verdict v = dropin_plan::resolve_span(c, offset, length, "write", &span)) return say(v);
+    const uint64_t nb = c.nb;
+    std::vector<uint64_t> off;
+    if (const dropin_plan::Verdict v = dropin_plan::walk_to(buf, in_total, c, nb, true, off)) return say(v);
+    if (snappy_status st = call.need_device()) return st;
+    const uint32_t dirty_max = (uint32_t)span.blocks;
+    const uint32_t bs_arg = c.total ? c.bs : 32768u;      // (an empty container's block size may be anything: nothing is sized by it)
+    // a dirty block grows to a slot at most, a clean one keeps its size
+    const uint64_t capacity = in_total + (uint64_t)dirty_max * snappy_hip_slot_stride(bs_arg) + 16;
+    const uint64_t scratch_bytes = snappy_hip_update_scratch_bytes(bs_arg, (uint32_t)nb, 1, std::max(1u, dirty_max));
+
+    uint8_t *d_stream = nullptr, *d_new = nullptr, *d_scratch = nullptr, *d_patch = nullptr;
+    uint64_t *d_boff = nullptr, *d_noff = nullptr;      // d_noff: the new offsets, then the new length
+    snappy_hip_stream_desc* d_desc = nullptr;
+    snappy_hip_write* d_write = nullptr;
+    uint32_t* d_words = nullptr;                        // [0] the write's status, [1..2] the result
+    if (snappy_status st = call.buffers({{&d_stream, in_total}, {&d_boff, (nb + 1) * sizeof(uint64_t)}, {&d_noff, (nb + 2) * sizeof(uint64_t)},
+                                         {&d_desc, sizeof *d_desc}, {&d_write, sizeof *d_write}, {&d_words, 4 * sizeof(uint32_t)},
+                                         {&d_patch, length}, {&d_new, capacity}, {&d_scratch, scratch_bytes}}))
+        return st;
+    const snappy_hip_stream_desc desc{d_stream, in_total, d_boff, nullptr, c.total, bs_arg, c.hdr, (uint32_t)nb};
+    const snappy_hip_write write{offset, length, d_patch, 0};
+    if (snappy_status st = call.upload({{d_stream, buf, in_total}, {d_boff, off.data(), (nb + 1) * sizeof(uint64_t)}, {d_desc, &desc, sizeof desc},
+                                        {d_write, &write, sizeof write}, {d_patch, patch->buffer, length}}))
+        return st;
+    if (snappy_status st = call.launch("update", [&] {
+            return snappy_hip_update_ranges(d_desc, c.total, bs_arg, d_write, 1, d_words, d_new, capacity, d_noff, d_noff + nb + 1, d_words + 1,
+                                            std::max(1u, dirty_max), d_scratch, scratch_bytes, nullptr);
+        }))
+        return st;
+    uint32_t words[3] = {0xffffffffu, 0xffffffffu, 0};
+    uint64_t new_len = 0;
+    snappy_status verdict = SNAPPY_OK;
+    if (snappy_status st = call.copy_out([&]() -> int {
+            if (int rc = call.download({{words, d_words, sizeof words}, {&new_len, d_noff + nb + 1, sizeof new_len}})) return rc;
+            if (words[0] != SNAPPY_HIP_BLOCK_OK || words[1] != SNAPPY_HIP_BLOCK_OK || new_len > capacity) {
+                fprintf(stderr, "snappy_hip: the stream cannot be updated (write status %u, result %u)\n", words[0], words[1]);
+                verdict = SNAPPY_INVALID_INPUT;
+                return 0;
+            }
+            if ((verdict = claim_output(output, new_len))) return 0;
+            return call.download({{output->buffer, d_new, new_len}});
+        }))
+        return st;
+    if (verdict) return verdict;
+    if (snappy_status st = call.free_buffers()) return st;
+    place(output, new_len);
+    return SNAPPY_OK;
+}
+
+// The raw ("original") Snappy format, one buffer each way: one item through the batch calls of snappy_raw.hpp.
 struct RawVerdict {            // what one item's call leaves on the device
     uint64_t out_len;
     uint32_t status;
@@ -942,17 +895,13 @@ struct RawVerdict {            // what one item's call leaves on the device
 snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
                            struct program_runtime* runtime)
 {
-    double t0 = now_seconds();
     if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
-    runtime->d_alloc = runtime->load = runtime->copy_in = runtime->run = runtime->copy_out = runtime->d_free = 0.0;
+    PhasedCall call(runtime);
     const uint64_t in_len = input->length;
     uint64_t capacity = 0, scratch_bytes = 0;
     uint32_t fragments = 0;
     if (compress) {
-        if (!block_size_ok(block_size)) {
-            fprintf(stderr, "snappy_hip: block size %u is outside 1..65535\n", block_size);
-            return SNAPPY_INVALID_INPUT;
-        }
+        if (!block_size_ok(block_size)) return say(dropin_plan::bad_block_size(block_size, ""));
         if (in_len >> 32) {
             fprintf(stderr, "snappy_hip: a raw Snappy stream holds less than 4 GiB\n");
             return SNAPPY_INVALID_INPUT;
@@ -962,79 +911,47 @@ snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, str
         scratch_bytes = snappy_hip_raw_compress_scratch_bytes(block_size, 1, fragments);
     } else {
         uint32_t length = 0;
-        const uint32_t hdr = get_varint32(input->buffer, in_len, &length);   // (the device reads it again, by Google's rule)
-        if (!hdr) {
-            fprintf(stderr, "Failed to read the stream header\n");
-            return SNAPPY_INVALID_INPUT;
-        }
+        if (!get_varint32(input->buffer, in_len, &length)) return say(dropin_plan::unreadable_header());   // (the device reads it again, by Google's rule)
         if (in_len > SNAPPY_HIP_RAW_MAX_LEN || length > SNAPPY_HIP_RAW_MAX_LEN) {
             fprintf(stderr, "snappy_hip: raw streams of more than %llu bytes are not decoded\n", (unsigned long long)SNAPPY_HIP_RAW_MAX_LEN);
             return SNAPPY_INVALID_INPUT;
         }
         capacity = length;
-        if (snappy_status st = raw_output_buffer(output, capacity)) return st;
+        if (snappy_status st = claim_output(output, capacity)) return st;      // decode knows its size now, compress after the launch
     }
-    output->length = 0;
-    output->curr = output->buffer;
-    if (snappy_hip_device_count() <= 0) {
-        fprintf(stderr, "snappy_hip: no HIP device available; the -d path has no CPU fallback\n");
-        return SNAPPY_INVALID_INPUT;
-    }
-    runtime->pre += now_seconds() - t0;
+    place(output, 0);
+    if (snappy_status st = call.need_device()) return st;
 
-    DeviceBuffers dev;
     uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
     snappy_hip_raw_item* d_item = nullptr;
     RawVerdict* d_verdict = nullptr;
-    double t = now_seconds();
-    if (dev.alloc((void**)&d_in, in_len) || dev.alloc((void**)&d_out, capacity) || dev.alloc((void**)&d_item, sizeof(snappy_hip_raw_item)) ||
-        dev.alloc((void**)&d_verdict, sizeof(RawVerdict)) || dev.alloc((void**)&d_scratch, scratch_bytes))
-        return report("device allocation");
-    runtime->d_alloc = now_seconds() - t;
-    t = now_seconds();
-    if (warm_up_device()) return report("code object load");
-    runtime->load = now_seconds() - t;
+    if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_out, capacity}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict},
+                                         {&d_scratch, scratch_bytes}}))
+        return st;
     const snappy_hip_raw_item item{d_in, in_len, d_out, capacity};
-    t = now_seconds();
-    if ((in_len && hipMemcpy(d_in, input->buffer, in_len, hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(d_item, &item, sizeof item, hipMemcpyHostToDevice) != hipSuccess) {
-        g_last_error = "hipMemcpy to the device";
-        return report("host-to-device copy");
-    }
-    runtime->copy_in = now_seconds() - t;
-    t = now_seconds();
-    const int launched = compress ? snappy_hip_raw_compress_batch(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
-                                                                  d_verdict->result, d_scratch, scratch_bytes, nullptr)
-                                  : snappy_hip_raw_decompress_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr);
-    if (launched != SNAPPY_HIP_OK) return report("raw batch launch");
-    if (hipDeviceSynchronize() != hipSuccess) {
-        g_last_error = "hipDeviceSynchronize after the raw batch";
-        return report("raw batch");
-    }
-    runtime->run = now_seconds() - t;
-    t = now_seconds();
+    if (snappy_status st = call.upload({{d_in, input->buffer, in_len}, {d_item, &item, sizeof item}})) return st;
+    if (snappy_status st = call.launch("raw batch", [&] {
+            return compress ? snappy_hip_raw_compress_batch(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
+                                                            d_verdict->result, d_scratch, scratch_bytes, nullptr)
+                            : snappy_hip_raw_decompress_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr);
+        }))
+        return st;
     RawVerdict v{};
-    if (hipMemcpy(&v, d_verdict, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_last_error = "hipMemcpy to the host";
-        return report("device-to-host copy");
-    }
-    if (v.status != SNAPPY_HIP_BLOCK_OK || v.out_len > capacity) {
-        fprintf(stderr, "snappy_hip: the raw stream cannot be %s (status %u)\n", compress ? "written" : "decoded", v.status);
-        return SNAPPY_INVALID_INPUT;
-    }
-    if (compress)
-        if (snappy_status st = raw_output_buffer(output, v.out_len)) return st;
-    if (v.out_len && hipMemcpy(output->buffer, d_out, v.out_len, hipMemcpyDeviceToHost) != hipSuccess) {
-        g_last_error = "hipMemcpy to the host";
-        return report("device-to-host copy");
-    }
-    runtime->copy_out = now_seconds() - t;
-    t = now_seconds();
-    for (void* p : dev.mem) (void)hipFree(p);
-    dev.mem.clear();
-    runtime->d_free = now_seconds() - t;
-    output->length = v.out_len;
-    output->curr = output->buffer + v.out_len;
+    snappy_status verdict = SNAPPY_OK;
+    if (snappy_status st = call.copy_out([&]() -> int {
+            if (int rc = call.download({{&v, d_verdict, sizeof v}})) return rc;
+            if (v.status != SNAPPY_HIP_BLOCK_OK || v.out_len > capacity) {
+                fprintf(stderr, "snappy_hip: the raw stream cannot be %s (status %u)\n", compress ? "written" : "decoded", v.status);
+                verdict = SNAPPY_INVALID_INPUT;
+                return 0;
+            }
+            if (compress && (verdict = claim_output(output, v.out_len))) return 0;
+            return call.download({{output->buffer, d_out, v.out_len}});
+        }))
+        return st;
+    if (verdict) return verdict;
+    if (snappy_status st = call.free_buffers()) return st;
+    place(output, v.out_len);
     return SNAPPY_OK;
 }
 

@@ -1,12 +1,14 @@
 // dropin_plan.hpp -- where the drop-in pair (csrc/dropin_pair.hpp) puts every byte.  Plain C++, no HIP, no environment
 // reads (the caller passes the knobs): tests/test_dropin_plan.py compiles it on the CPU.
 #pragma once
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <string>
 #include <vector>
+#include "../../include/snappy_hip.h"
 #include "host_chain.hpp"
 
 namespace dropin_plan {
@@ -79,7 +81,30 @@ inline std::vector<Range> split_blocks(uint64_t nb, uint64_t plain_len, uint32_t
     return cut(nb, per, (nb + per - 1) / per, plain_len, bs);
 }
 
-inline uint32_t varint32_len(uint32_t v)   // bytes of put_varint32 (snappy_compress.c:69-98)
+inline uint32_t put_varint32(uint8_t* dst, uint32_t v)   // snappy_compress.c:69-98
+{
+    uint32_t k = 0;
+    while (v >= 0x80) {
+        dst[k++] = (uint8_t)(v | 0x80);
+        v >>= 7;
+    }
+    dst[k++] = (uint8_t)v;
+    return k;
+}
+inline uint32_t get_varint32(const uint8_t* src, uint64_t avail, uint32_t* out)   // snappy_decompress.c:23-37; 0 = unreadable
+{
+    uint32_t v = 0;
+    for (uint32_t k = 0; k < 5 && k < avail; ++k) {
+        const uint8_t c = src[k];
+        v |= (uint32_t)(c & 0x7f) << (7 * k);
+        if (!(c & 0x80)) {
+            *out = v;
+            return k + 1;
+        }
+    }
+    return 0;
+}
+inline uint32_t varint32_len(uint32_t v)   // bytes of put_varint32
 {
     uint32_t k = 1;
     for (; v >= 0x80; v >>= 7) ++k;
@@ -139,6 +164,87 @@ inline std::string whole_walk_error(const Walk& w, uint64_t nb, uint64_t len)
     else if (w.at != len)
         snprintf(m, sizeof m, "size chain ends at %lu, stream has %lu bytes", (unsigned long)w.at, (unsigned long)len);
     return m;
+}
+
+// ---- The front end of the single-device calls on one framed file (byte-range decode, byte-range overwrite): what the host
+// decides about an untrusted container before anything is sized by it or sent to a device. ----
+
+inline bool block_size_ok(uint32_t bs) { return bs >= SNAPPY_HIP_MIN_BLOCK_SIZE && bs <= SNAPPY_HIP_MAX_BLOCK_SIZE; }
+
+// What a check decided: the status for the caller and the line for stderr (this file prints nothing).
+struct Verdict {
+    snappy_status status = SNAPPY_OK;
+    std::string message;
+    explicit operator bool() const { return status != SNAPPY_OK; }
+};
+__attribute__((format(printf, 1, 2))) inline Verdict refuse(const char* fmt, ...)
+{
+    char m[160] = "snappy_hip: ";
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(m + 12, sizeof m - 12, fmt, ap);
+    va_end(ap);
+    return {SNAPPY_INVALID_INPUT, m};
+}
+inline Verdict unreadable_header() { return {SNAPPY_INVALID_INPUT, "Failed to read the stream header"}; }   // the reference's words
+inline Verdict bad_block_size(uint32_t bs, const char* where) { return refuse("block size %u%s is outside 1..65535", bs, where); }
+
+// the two varints in front of the first block (snappy_decompress.c:193-198, :298-303); 0 = unreadable
+inline uint32_t parse_header(const uint8_t* buf, uint64_t len, uint32_t* total, uint32_t* bs)
+{
+    const uint32_t a = get_varint32(buf, len, total);
+    const uint32_t b = a ? get_varint32(buf + a, len - a, bs) : 0;
+    return b ? a + b : 0;
+}
+
+// A framed file: header bytes, uncompressed bytes, block size, blocks.  `bad` = the header cannot be read (hdr = 0), or the
+// file has bytes and its block size is outside 1..65535 (hdr != 0, nb = 0).  The functions below return it where it first
+// matters to them: resolve_span an unreadable header, walk_to either -- so a span beyond the file is refused as such, and
+// an empty range served, whatever the block size says.
+struct Container {
+    uint32_t hdr = 0, total = 0, bs = 0;
+    uint64_t nb = 0;
+    Verdict bad;
+};
+inline Container open_container(const uint8_t* buf, uint64_t len)
+{
+    Container c;
+    c.hdr = parse_header(buf, len, &c.total, &c.bs);
+    if (!c.hdr)
+        c.bad = unreadable_header();
+    else if (c.total && !block_size_ok(c.bs))
+        c.bad = bad_block_size(c.bs, " in the stream");
+    else if (c.total)
+        c.nb = ((uint64_t)c.total + c.bs - 1) / c.bs;
+    return c;
+}
+
+// the blocks that plaintext bytes [offset, offset + length) touch: none for an empty span (or while c.bad)
+struct Span { uint64_t first = 0, last = 0, blocks = 0; };
+inline Verdict resolve_span(const Container& c, uint64_t offset, uint64_t length, const char* what, Span* s)
+{
+    *s = Span{};
+    if (!c.hdr) return c.bad;
+    if (offset + length < offset || offset + length > c.total)
+        return refuse("%s %lu:%lu lies beyond the %u uncompressed bytes", what, (unsigned long)offset, (unsigned long)length, c.total);
+    if (length && c.nb) *s = {offset / c.bs, (offset + length - 1) / c.bs, (offset + length - 1) / c.bs - offset / c.bs + 1};
+    return {};
+}
+
+// The size chain from the header up to block `upto`: off[i] = stream offset of block i for i < upto, off[upto] = where the chain
+// then stands.  Every block needs its u32 size prefix, which is checked before anything is sized by the header-derived
+// count.  A walk that stops names the first block whose prefix is not in the stream (the one after a block that leaves it).
+// to_the_end: the chain must end exactly where the stream does.
+inline Verdict walk_to(const uint8_t* buf, uint64_t len, const Container& c, uint64_t upto, bool to_the_end, std::vector<uint64_t>& off)
+{
+    if (c.bad) return c.bad;
+    if (upto > (len - c.hdr) / 4) return refuse("truncated stream (block %lu of %lu)", (unsigned long)(upto - 1), (unsigned long)c.nb);
+    off.assign(upto + 1, 0);
+    const Walk w = walk_chain(buf, len, 0, off.data(), {0, c.hdr}, upto);
+    if (w.stop != kDone)
+        return refuse("truncated stream (block %lu of %lu)", (unsigned long)(w.stop == kLeaves ? w.block + 1 : w.block), (unsigned long)c.nb);
+    if (to_the_end && w.at != len) return refuse("%lu bytes behind the last block", (unsigned long)(len - w.at));
+    return {};
 }
 
 }  // namespace dropin_plan

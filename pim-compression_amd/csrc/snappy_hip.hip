@@ -53,32 +53,9 @@ double now_seconds()
     return (double)tv.tv_sec + (double)tv.tv_usec / 1000000.0;
 }
 
-uint32_t put_varint32(uint8_t* dst, uint32_t v)   // snappy_compress.c:69-98
-{
-    uint32_t k = 0;
-    while (v >= 0x80) {
-        dst[k++] = (uint8_t)(v | 0x80);
-        v >>= 7;
-    }
-    dst[k++] = (uint8_t)v;
-    return k;
-}
-
-uint32_t get_varint32(const uint8_t* src, uint64_t avail, uint32_t* out)   // snappy_decompress.c:23-37
-{
-    uint32_t v = 0;
-    for (uint32_t k = 0; k < 5 && k < avail; ++k) {
-        const uint8_t c = src[k];
-        v |= (uint32_t)(c & 0x7f) << (7 * k);
-        if (!(c & 0x80)) {
-            *out = v;
-            return k + 1;
-        }
-    }
-    return 0;
-}
-
-bool block_size_ok(uint32_t bs) { return bs >= SNAPPY_HIP_MIN_BLOCK_SIZE && bs <= SNAPPY_HIP_MAX_BLOCK_SIZE; }
+using dropin_plan::block_size_ok;
+using dropin_plan::get_varint32;   // (one home for the varints and the header: csrc/dropin_plan.hpp)
+using dropin_plan::put_varint32;
 
 // Run fn(g) for g in [0, count) -- one host thread per device when count > 1 (pageable
 // hipMemcpy is synchronous per call, so threads are what overlaps the per-GPU transfers).
@@ -485,11 +462,7 @@ uint32_t snappy_hip_write_header(uint8_t* dst, uint32_t total_len, uint32_t bloc
 
 uint32_t snappy_hip_parse_header(const uint8_t* src, uint64_t avail, uint32_t* total_len, uint32_t* block_size)
 {
-    const uint32_t a = get_varint32(src, avail, total_len);
-    if (!a) return 0;
-    const uint32_t b = get_varint32(src + a, avail - a, block_size);
-    if (!b) return 0;
-    return a + b;
+    return dropin_plan::parse_header(src, avail, total_len, block_size);
 }
 
 #ifdef SNAPPY_ABLATION

@@ -7,7 +7,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import container_cases as cc
 import datagen
+import oracle_lib as oracle
 import ranges_cases as rc
 from conftest import golden_bytes
 
@@ -235,3 +237,21 @@ def test_gpu_dropin_and_cli_range_match_host_mode(shb, tmp_path):
     assert st == shb.SNAPPY_INVALID_INPUT
     r_d, dev = _cli_range(["-d", "-r", "5345280:1", "-i", os.path.join(ROOT, "tests", "golden", "xml.snappy")], tmp_path, "beyond")
     assert r_d.returncode != 0 and r_d.stderr.strip() and dev is None
+    # coding.txt at 1000-byte blocks, a span through blocks 2..4: each damaged variant gets the status that the front end's CPU
+    # test (tests/test_dropin_plan.py) holds to the model -- decided on the host, so damage behind block 4 does not matter
+    plain = golden_bytes("coding.txt")
+    stream = oracle.compress(plain, 1000)
+    off, n = cc.inner_span(1000)
+    variants = cc.damaged(stream)
+    variants["cut after block 4"] = stream[:cc.chain(stream)[5]]
+    for kind, bad in variants.items():
+        st, got, _ = shb.decompress_range_host(bad, off, n)
+        assert st == cc.model(bad, off, n, update=False)[0], kind
+        assert got == (plain[off:off + n] if st == 0 else b""), kind
+    served = [kind for kind, bad in variants.items() if cc.model(bad, off, n, update=False)[0] == 0]
+    assert served == ["intact", "cut in a size prefix", "cut in a body", "7 trailing bytes", "a middle size field of 0x7ffffff0",
+                      "cut after block 4"]
+    st, _, _ = shb.decompress_range_host(stream, off, n, out_capacity=n - 1)
+    assert st == shb.SNAPPY_BUFFER_TOO_SMALL
+    st, got, _ = shb.decompress_range_host(stream, off, n, out_capacity=n)
+    assert st == 0 and got == plain[off:off + n]

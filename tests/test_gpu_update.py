@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import container_cases as cc
 import datagen
 import oracle_lib as oracle
 import ranges_cases as rc
@@ -399,3 +400,18 @@ def test_gpu_dropin_and_cli_update_match_host_mode(shb, tmp_path):
     pf.write_bytes(patch)
     r_d, dev = _cli_update(["-d", "-w", f"{total - 50}:{pf}", "-i", path], tmp_path, "beyond.out")
     assert r_d.returncode != 0 and r_d.stderr.strip() and dev is None
+    # coding.txt at 1000-byte blocks, a write through blocks 2..4: each damaged variant gets the status that the front end's CPU
+    # test (tests/test_dropin_plan.py) holds to the model -- an update walks the whole chain, so only the intact one passes
+    plain = golden_bytes("coding.txt")
+    stream = oracle.compress(plain, 1000)
+    off, n = cc.inner_span(1000)
+    patch = uc.new_bytes(plain, off, n, "random", seed=9)
+    want = oracle.compress(uc.patched(plain, [(off, patch)]), 1000)
+    for kind, bad in cc.damaged(stream).items():
+        st, got, _ = shb.update_range_host(bad, off, patch)
+        assert st == cc.model(bad, off, n, update=True)[0] == (0 if kind == "intact" else shb.SNAPPY_INVALID_INPUT), kind
+        assert got == (want if st == 0 else b""), kind
+    st, _, _ = shb.update_range_host(stream, off, patch, out_capacity=len(want) - 1)
+    assert st == shb.SNAPPY_BUFFER_TOO_SMALL
+    st, got, _ = shb.update_range_host(stream, off, patch, out_capacity=len(want))
+    assert st == 0 and got == want
