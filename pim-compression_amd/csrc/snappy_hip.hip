@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/snappy_hip.h"
@@ -165,6 +166,25 @@ int work_counter_launched(const WorkCounter& c, hipStream_t st)
     return 0;
 }
 
+// One launch of a persistent kernel on a counter of its own: launch(counter) enqueues the kernel on `st` and returns 0, or
+// refuses with fail(...) before it launches anything (the counter is handed back, the refusal is what the caller hears).
+// A failure of the counter (taking it, or handing it back) is reported before the launch's own error.
+template <class Launch>
+int launch_counted(hipStream_t st, Launch launch)
+{
+    WorkCounter wc;
+    if (int rc = next_work_counter(&wc, st)) return rc;
+    if (int rc = launch(wc.ptr)) {
+        const std::string refusal = g_last_error;
+        (void)work_counter_launched(wc, st);
+        return fail(rc, refusal);
+    }
+    const hipError_t launched = hipGetLastError();
+    if (int rc = work_counter_launched(wc, st)) return rc;
+    HIP_TRY(launched);
+    return 0;
+}
+
 // Helper stream + fork/join events for launches that co-run two kernels, one set per (host thread, device).  The
 // events are timing-disabled; the helper stream is non-blocking, so the only ordering is the explicit fork (ev_begin)
 // and join (ev_end) around the caller's stream.
@@ -270,11 +290,21 @@ int k1_stream_forms(uint32_t block_size)
     return env_int("SNAPPY_HIP_K1_STREAM", kDefaultK1Stream | (gt_cache_slots(block_size) ? 2 : 0));
 }
 
+// The form of K1's parse the LDS-table wavefronts run at this block size, and the dynamic LDS that goes with it:
+// fn(std::integral_constant<int, form>, lds_bytes), form 3 = stream, 2 = bulk (LDS_TABLE_WAVE_COMPRESS, snappy_kernels.hpp)
+template <class Fn>
+void with_lds_table_form(uint32_t block_size, Fn fn)
+{
+    if (k1_stream_forms(block_size) & 1) fn(std::integral_constant<int, 3>(), snappy_hip::lds_table_stream_lds_bytes(block_size));
+    else fn(std::integral_constant<int, 2>(), snappy_hip::lds_table_kernel_lds_bytes(block_size, true));
+}
+
 // dynamic LDS of one LDS-table workgroup of the product's launch at this block size
 uint32_t lds_table_wave_bytes(uint32_t block_size)
 {
-    return (k1_stream_forms(block_size) & 1) ? snappy_hip::lds_table_stream_lds_bytes(block_size)
-                                             : snappy_hip::lds_table_kernel_lds_bytes(block_size, true);
+    uint32_t bytes = 0;
+    with_lds_table_form(block_size, [&](auto, uint32_t lds) { bytes = lds; });
+    return bytes;
 }
 
 uint32_t default_lds_waves_per_cu(uint32_t block_size)
@@ -345,12 +375,10 @@ int check_knobs()
 void launch_lds_table_kernel(uint32_t grid, hipStream_t st, const snappy_hip::K1Batch& w, uint32_t block_size, uint32_t slot_stride,
                              uint32_t* counter)
 {
-    if (k1_stream_forms(block_size) & 1)
-        hipLaunchKernelGGL((snappy_hip::compress_blocks_lds_table_kernel<64, 3>), dim3(grid), dim3(64),
-                           snappy_hip::lds_table_stream_lds_bytes(block_size), st, w, block_size, slot_stride, counter);
-    else
-        hipLaunchKernelGGL((snappy_hip::compress_blocks_lds_table_kernel<64, 2>), dim3(grid), dim3(64),
-                           snappy_hip::lds_table_kernel_lds_bytes(block_size, true), st, w, block_size, slot_stride, counter);
+    with_lds_table_form(block_size, [&](auto form, uint32_t lds) {
+        hipLaunchKernelGGL((snappy_hip::compress_blocks_lds_table_kernel<64, form()>), dim3(grid), dim3(64), lds, st, w, block_size, slot_stride,
+                           counter);
+    });
 }
 
 void launch_global_table_kernel(uint32_t grid, hipStream_t st, const snappy_hip::K1Batch& w, uint32_t block_size, uint32_t slot_stride,
@@ -740,22 +768,16 @@ static int launch_decompress(const snappy_hip::K2Batch& w, uint32_t block_size, 
     // every block's status starts as "not decoded": a block the launch never reaches cannot read back as OK
     for (uint32_t c = 0; c < w.count; ++c)
         HIP_TRY(hipMemsetAsync(w.status[c], 0xff, (size_t)(w.first_block[c + 1] - w.first_block[c]) * sizeof(uint32_t), st));
-    WorkCounter wc;
-    if (int rc = next_work_counter(&wc, st)) return rc;
-    uint32_t* counter = wc.ptr;
-    const launch_shape::DeviceShape shape = device_shape();
-    const uint32_t k2_cap = (uint32_t)std::max(1, env_int("SNAPPY_HIP_K2_WAVES", (int)shape.wave_slots()));   // fewer wavefronts leave slots for a co-running kernel
-    if (getenv("SNAPPY_HIP_DECOMPRESS_VARIANT") || getenv("SNAPPY_HIP_K2_BATCH") || getenv("SNAPPY_HIP_K2_LDS_WAVES")) {
-        (void)work_counter_launched(wc, st);
-        return fail(SNAPPY_HIP_ERR_ARG, "SNAPPY_HIP_DECOMPRESS_VARIANT / SNAPPY_HIP_K2_BATCH / SNAPPY_HIP_K2_LDS_WAVES selected decoder forms of "
-                                        "rounds 1-2 that were removed in round 4 (profiles/HISTORY.md)");
-    }
-    hipLaunchKernelGGL(snappy_hip::decompress_blocks_kernel, dim3(launch_shape::k2_launch_waves(shape, nb, (int)k2_cap)), dim3(64), 0, st, w,
-                       block_size, counter);
-    const hipError_t launched = hipGetLastError();
-    if (int rc = work_counter_launched(wc, st)) return rc;
-    HIP_TRY(launched);
-    return SNAPPY_HIP_OK;
+    return launch_counted(st, [&](uint32_t* counter) {
+        const launch_shape::DeviceShape shape = device_shape();
+        const uint32_t k2_cap = (uint32_t)std::max(1, env_int("SNAPPY_HIP_K2_WAVES", (int)shape.wave_slots()));   // fewer wavefronts leave slots for a co-running kernel
+        if (getenv("SNAPPY_HIP_DECOMPRESS_VARIANT") || getenv("SNAPPY_HIP_K2_BATCH") || getenv("SNAPPY_HIP_K2_LDS_WAVES"))
+            return fail(SNAPPY_HIP_ERR_ARG, "SNAPPY_HIP_DECOMPRESS_VARIANT / SNAPPY_HIP_K2_BATCH / SNAPPY_HIP_K2_LDS_WAVES selected decoder forms of "
+                                            "rounds 1-2 that were removed in round 4 (profiles/HISTORY.md)");
+        hipLaunchKernelGGL(snappy_hip::decompress_blocks_kernel, dim3(launch_shape::k2_launch_waves(shape, nb, (int)k2_cap)), dim3(64), 0, st, w,
+                           block_size, counter);
+        return 0;
+    });
 }
 
 static int check_stream(const void* d_stream, const void* d_block_offsets, uint64_t total_len, uint32_t block_size, const void* d_out,
@@ -853,15 +875,12 @@ int snappy_hip_decompress_ranges(const snappy_hip_stream_desc* d_descs, uint32_t
     hipLaunchKernelGGL(snappy_hip::range_pieces_kernel, dim3(1), dim3(1024), 0, st, descs, count, ranges, range_count, d_status, max_block_size,
                        prefix);
     HIP_TRY(hipGetLastError());
-    WorkCounter wc;
-    if (int rc = next_work_counter(&wc, st)) return rc;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(range_grid_cap(), slots);
-    hipLaunchKernelGGL(snappy_hip::decompress_ranges_kernel, dim3(grid), dim3(64), 0, st, descs, ranges, range_count, d_status, prefix,
-                       slot_base, (uint32_t)slot_bytes, wc.ptr);
-    const hipError_t launched = hipGetLastError();
-    if (int rc = work_counter_launched(wc, st)) return rc;
-    HIP_TRY(launched);
-    return SNAPPY_HIP_OK;
+    return launch_counted(st, [&](uint32_t* counter) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(range_grid_cap(), slots);
+        hipLaunchKernelGGL(snappy_hip::decompress_ranges_kernel, dim3(grid), dim3(64), 0, st, descs, ranges, range_count, d_status, prefix,
+                           slot_base, (uint32_t)slot_bytes, counter);
+        return 0;
+    });
 }
 
 // ---- overwriting byte ranges (snappy_update.hpp) ----
@@ -913,19 +932,14 @@ int snappy_hip_update_ranges(const snappy_hip_stream_desc* d_desc, uint32_t tota
                        d_write_status, max_dirty_blocks, ctl, span, rank, dirty, d_new_stream_len, d_result);
     HIP_TRY(hipGetLastError());
     if (write_count && nb) {
-        WorkCounter wc;
-        if (int rc = next_work_counter(&wc, st)) return rc;
-        if (k1_stream_forms(block_size) & 1)
-            hipLaunchKernelGGL(snappy_hip::recompress_dirty_kernel<3>, dim3(waves), dim3(64), snappy_hip::lds_table_stream_lds_bytes(block_size), st,
-                               desc, total_len, block_size, writes, write_count, ctl, dirty, dirty_bytes, scratch + l.patch, l.patch_slot_bytes,
-                               scratch + l.cslots, stride, wc.ptr);
-        else
-            hipLaunchKernelGGL(snappy_hip::recompress_dirty_kernel<2>, dim3(waves), dim3(64), snappy_hip::lds_table_kernel_lds_bytes(block_size, true),
-                               st, desc, total_len, block_size, writes, write_count, ctl, dirty, dirty_bytes, scratch + l.patch,
-                               l.patch_slot_bytes, scratch + l.cslots, stride, wc.ptr);
-        const hipError_t launched = hipGetLastError();
-        if (int rc = work_counter_launched(wc, st)) return rc;
-        HIP_TRY(launched);
+        const int rc = launch_counted(st, [&](uint32_t* counter) {
+            with_lds_table_form(block_size, [&](auto form, uint32_t lds) {
+                hipLaunchKernelGGL(snappy_hip::recompress_dirty_kernel<form()>, dim3(waves), dim3(64), lds, st, desc, total_len, block_size, writes,
+                                   write_count, ctl, dirty, dirty_bytes, scratch + l.patch, l.patch_slot_bytes, scratch + l.cslots, stride, counter);
+            });
+            return 0;
+        });
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(snappy_hip::update_sizes_kernel, dim3(1), dim3(1024), 0, st, total_len, block_size, nb, ctl, span, rank, dirty_bytes,
                        d_new_stream, new_stream_capacity, d_new_offsets, d_new_stream_len, d_result);
@@ -945,15 +959,12 @@ int snappy_hip_raw_decompress_batch(const snappy_hip_raw_item* d_items, uint32_t
     if (count == 0) return SNAPPY_HIP_OK;
     if (!d_items || !d_out_len || !d_status) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
     hipStream_t st = (hipStream_t)stream;
-    WorkCounter wc;
-    if (int rc = next_work_counter(&wc, st)) return rc;
-    const uint32_t grid = std::min(range_grid_cap(), count);
-    hipLaunchKernelGGL(snappy_hip::raw_decompress_kernel, dim3(grid), dim3(64), 0, st, reinterpret_cast<const snappy_hip::RawItem*>(d_items), count,
-                       d_out_len, d_status, wc.ptr);
-    const hipError_t launched = hipGetLastError();
-    if (int rc = work_counter_launched(wc, st)) return rc;
-    HIP_TRY(launched);
-    return SNAPPY_HIP_OK;
+    return launch_counted(st, [&](uint32_t* counter) {
+        const uint32_t grid = std::min(range_grid_cap(), count);
+        hipLaunchKernelGGL(snappy_hip::raw_decompress_kernel, dim3(grid), dim3(64), 0, st, reinterpret_cast<const snappy_hip::RawItem*>(d_items), count,
+                           d_out_len, d_status, counter);
+        return 0;
+    });
 }
 
 uint64_t snappy_hip_raw_compress_bound(uint64_t src_len, uint32_t block_size)
@@ -998,21 +1009,15 @@ int snappy_hip_raw_compress_batch(const snappy_hip_raw_item* d_items, uint32_t c
         HIP_TRY(hipGetLastError());
         return SNAPPY_HIP_OK;
     }
-    {
-        WorkCounter wc;
-        if (int rc = next_work_counter(&wc, st)) return rc;
-        const uint32_t waves = std::min(launch_shape::update_resident_waves(device_shape(), lds_table_wave_bytes(block_size)), max_fragments);
-        if (k1_stream_forms(block_size) & 1)
-            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<3>, dim3(waves), dim3(64), snappy_hip::lds_table_stream_lds_bytes(block_size),
-                               st, items, count, block_size, ctl, prefix, frag_bytes, scratch + l.slots, stride, wc.ptr);
-        else
-            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<2>, dim3(waves), dim3(64),
-                               snappy_hip::lds_table_kernel_lds_bytes(block_size, true), st, items, count, block_size, ctl, prefix, frag_bytes,
-                               scratch + l.slots, stride, wc.ptr);
-        const hipError_t launched = hipGetLastError();
-        if (int rc = work_counter_launched(wc, st)) return rc;
-        HIP_TRY(launched);
-    }
+    const int rc = launch_counted(st, [&](uint32_t* counter) {
+        with_lds_table_form(block_size, [&](auto form, uint32_t lds) {
+            const uint32_t waves = std::min(launch_shape::update_resident_waves(device_shape(), lds), max_fragments);
+            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<form()>, dim3(waves), dim3(64), lds, st, items, count, block_size, ctl, prefix,
+                               frag_bytes, scratch + l.slots, stride, counter);
+        });
+        return 0;
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(snappy_hip::raw_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, items, count, prefix, frag_bytes, place, d_out_len,
                        d_status, d_result);
     hipLaunchKernelGGL(snappy_hip::raw_gather_kernel, dim3(std::min(max_fragments, 32768u)), dim3(256), 0, st, items, count, ctl, prefix, frag_bytes,

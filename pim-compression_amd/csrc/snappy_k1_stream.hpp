@@ -90,14 +90,6 @@ constexpr uint32_t kStreamRoom = 192;   // the stream form takes a window when b
 constexpr uint32_t kStreamSlotsLds = SNAPPY_STREAM_SLOTS_LDS, kStreamSlotsGlobal = 256;
 __host__ __device__ constexpr uint32_t stream_scratch_bytes(uint32_t slots) { return 8u * slots; }
 
-// unaligned 16-byte load (gfx950 runs with unaligned VMEM access enabled: one global_load_dwordx4)
-__device__ __forceinline__ uint4 ld128(const uint8_t* p)
-{
-    uint4 v;
-    __builtin_memcpy(&v, p, 16);
-    return v;
-}
-
 struct StreamWindow {
     uint32_t base;          // window base (multiple of 64)
     uint4 a, b;             // per lane: le32(blk + base + lane + 0 / 4 / 8 / 12) and (+ 16 / 20 / 24 / 28)

@@ -22,9 +22,10 @@
 #include <stdlib.h>
 #endif
 
+#include "snappy_device_common.hpp"   // kWave, uni, ld32 ... ld128, draw_work, the scans, the varints
+
 namespace snappy_hip {
 
-constexpr uint32_t kWave = 64;
 constexpr uint32_t kMaxTableEntries = 16384;   // snappy_compress.c:16-17
 constexpr uint32_t kHashMul = 0x1e35a7bdu;     // snappy_compress.c:163
 constexpr uint32_t kInputMargin = 15;          // snappy_compress.c:299
@@ -39,36 +40,7 @@ constexpr uint32_t kInputMargin = 15;          // snappy_compress.c:299
 
 constexpr uint32_t kBlockOk = 0;
 constexpr uint32_t kBlockInvalid = 1;
-
-// ---------------------------------------------------------------------------
-// small device helpers
-// ---------------------------------------------------------------------------
-
-// broadcast lane 0's value; marks the value wave-uniform for the compiler (SGPR)
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// unaligned little-endian loads (gfx950 runs with unaligned VMEM/DS access enabled)
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p)
-{
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-__device__ __forceinline__ uint64_t ld64(const uint8_t* p)
-{
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-__device__ __forceinline__ void st32(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
-
-// wave-uniform load of 4 bytes at a uniform address
-__device__ __forceinline__ uint32_t uld32(const uint8_t* p) { return uni(ld32(p)); }
-__device__ __forceinline__ uint64_t uld64(const uint8_t* p)
-{
-    const uint64_t v = ld64(p);
-    return (uint64_t)uni((uint32_t)v) | ((uint64_t)uni((uint32_t)(v >> 32)) << 32);
-}
+constexpr uint32_t kRangeOutOfBounds = 2;      // SNAPPY_HIP_RANGE_OUT_OF_BOUNDS: a range or a write beyond its container
 
 // hash-table sizing rule, snappy_compress.c:139-146
 __device__ __forceinline__ uint32_t table_entries_for(uint32_t n)
@@ -1160,6 +1132,33 @@ __host__ __device__ inline uint32_t lds_table_stream_lds_bytes(uint32_t block_si
     return 2u * lds_table_entries(block_size) + stream_scratch_bytes(kStreamSlotsLds);
 }
 
+// One wavefront of K1's LDS-table form, wherever it runs (the kernel below, the update's recompress kernel, the raw format's
+// fragment kernel): the u16 table of lds_table_entries(block_size) entries at the start of the dynamic LDS, the scratch of the
+// parse behind it.
+struct LdsTableWave {
+    LdsTable table;
+    lds_bytes_t scratch;
+    __device__ __forceinline__ LdsTableWave(uint8_t* lds_dyn, uint32_t block_size)
+        : table{reinterpret_cast<uint16_t*>(lds_dyn)}, scratch((lds_bytes_t)(lds_dyn + 2u * lds_table_entries(block_size))) {}
+};
+// LDS_TABLE_WAVE_COMPRESS(kForm, wave, src, start, src_len, n, out, lane, bytes_out): the n bytes at src + start (of src_len: K1's
+// loads are clamped to it) as one block into `out`, *bytes_out = 4 + size.  kForm: the form of the parse, 3 = stream (launched
+// with lds_table_stream_lds_bytes(block_size) of dynamic LDS), 2 = bulk (lds_table_kernel_lds_bytes(block_size, true)).
+// A macro, not a member function: through one more inlined call the same instructions come out in another order in all three
+// kernels, and the product kernel is held to the measured code instruction for instruction (tools/kernel_asm_diff.py).
+#define LDS_TABLE_WAVE_COMPRESS(kForm, wave, src, start, src_len, n, out, lane, bytes_out)                                                 \
+    do {                                                                                                                                    \
+        static_assert(kForm == 2 || kForm == 3, "the bulk (2) and the stream (3) form of the parse exist; rounds 1-2's other forms are in " \
+                                                "the history (profiles/HISTORY.md)");                                                      \
+        if constexpr (kForm == 3) {                                                                                                         \
+            SoloMate solo;                                                                                                                  \
+            compress_one_block_stream<LdsTable, kStreamSlotsLds>(src, start, src_len, n, out, (wave).table, lane, bytes_out, (wave).scratch, \
+                                                                 solo);                                                                     \
+        } else {                                                                                                                            \
+            compress_one_block_bulk<LdsTable, 64>(src, start, src_len, n, out, (wave).table, lane, bytes_out, (wave).scratch);              \
+        }                                                                                                                                   \
+    } while (0)
+
 // next_block == nullptr: static grid-stride assignment; otherwise blocks are drawn from the shared atomic counter,
 // which lets this kernel run CONCURRENTLY with compress_blocks_global_table_kernel on the same container (the
 // LDS-table waves fill 5 wave slots per CU with low-latency tables, the global-table waves the other 27).
@@ -1172,9 +1171,9 @@ __global__ __launch_bounds__(64) void compress_blocks_lds_table_kernel(const K1B
     // table_entries_for(block_size) entries -- 512 B for -b 256 ... 32 KiB from -b 16384 up, as the reference sizes its
     // table to the block (snappy_compress.c:139-146; dpu_compress.c:472-476 to the tasklet's memory) -- then the 1 KiB
     // duplicate-slot scratch of the masked / bulk forms.  Small block sizes therefore fit many more of these wavefronts per CU.
+    static_assert(kAhead == 64, "the bulk form's chunk is one window (LDS_TABLE_WAVE_COMPRESS)");
     HIP_DYNAMIC_SHARED(uint8_t, lds_dyn)
-    uint16_t* table = reinterpret_cast<uint16_t*>(lds_dyn);
-    uint8_t* dup_scratch = lds_dyn + 2u * lds_table_entries(block_size);
+    const LdsTableWave k1(lds_dyn, block_size);
     const uint32_t lane = threadIdx.x;
 #ifndef SNAPPY_EMU
     // The LDS-table wavefronts are few (LDS capacity) but cost no table traffic: let the instruction arbiter prefer them
@@ -1183,11 +1182,7 @@ __global__ __launch_bounds__(64) void compress_blocks_lds_table_kernel(const K1B
 #endif
     uint32_t b = blockIdx.x;
     for (;;) {
-        if (next_block) {
-            uint32_t drawn = 0;
-            if (lane == 0) drawn = atomicAdd(next_block, 1u);
-            b = uni(drawn);
-        }
+        if (next_block) b = draw_work(next_block, lane);
         if (b >= num_blocks) break;
         const uint32_t c = batch_container_of(w, b);
         const uint32_t lb = b - w.first_block[c];
@@ -1198,16 +1193,7 @@ __global__ __launch_bounds__(64) void compress_blocks_lds_table_kernel(const K1B
         const uint64_t start = (uint64_t)lb * block_size;
         const uint64_t left = in_len - start;
         const uint32_t n = (left < block_size) ? (uint32_t)left : block_size;
-        static_assert(kForm == 2 || kForm == 3, "the bulk (2) and the stream (3) form of the parse exist; rounds 1-2's other forms are in the history (profiles/HISTORY.md)");
-        if constexpr (kForm == 3)   // (launched with lds_table_stream_lds_bytes(block_size) of dynamic LDS)
-        {
-            SoloMate solo;
-            compress_one_block_stream<LdsTable, kStreamSlotsLds>(in, start, in_len, n, slot, LdsTable{table}, lane, bytes_out,
-                                                                 (lds_bytes_t)dup_scratch, solo);
-        }
-        else
-            compress_one_block_bulk<LdsTable, kAhead>(in, start, in_len, n, slot, LdsTable{table}, lane, bytes_out,
-                                                      (lds_bytes_t)dup_scratch);
+        LDS_TABLE_WAVE_COMPRESS(kForm, k1, in, start, in_len, n, slot, lane, bytes_out);
         if (next_block && lane == 0) atomicAdd(next_block + 4, 1u);   // statistics: blocks taken by the LDS-table form
         __syncthreads();
         b += gridDim.x;
@@ -1239,9 +1225,7 @@ __global__ __launch_bounds__(64) void compress_blocks_global_table_kernel(const 
         table.empty = 0;
     }
     for (;;) {
-        uint32_t b = 0;
-        if (lane == 0) b = atomicAdd(next_block, 1u);
-        b = uni(b);
+        const uint32_t b = draw_work(next_block, lane);
         if (b >= num_blocks) break;
         const uint32_t c = batch_container_of(w, b);
         const uint32_t lb = b - w.first_block[c];
@@ -1278,48 +1262,22 @@ __global__ __launch_bounds__(1024) void scan_block_bytes_kernel(const uint32_t* 
                                                                 uint64_t* __restrict__ stream_len)
 {
     __shared__ uint64_t wave_sums[16];
-    __shared__ uint64_t carry_s;
     const uint32_t tid = threadIdx.x;
-    const uint32_t lane = tid & 63, wave = tid >> 6;
 
     // header: at most 5 + 5 bytes, thread 0
-    uint32_t hdr_len = 0;
-    {
-        uint8_t hb[10];
-        uint32_t v = total_len;
-        while (v >= 0x80) { hb[hdr_len++] = (uint8_t)(v | 0x80); v >>= 7; }
-        hb[hdr_len++] = (uint8_t)v;
-        v = block_size;
-        while (v >= 0x80) { hb[hdr_len++] = (uint8_t)(v | 0x80); v >>= 7; }
-        hb[hdr_len++] = (uint8_t)v;
-        if (tid == 0)
-            for (uint32_t i = 0; i < hdr_len; ++i) stream[i] = hb[i];
-    }
-    if (tid == 0) carry_s = hdr_len;
-    __syncthreads();
+    if (tid == 0) put_varint32(stream + put_varint32(stream, total_len), block_size);
+    uint64_t carry = varint32_len(total_len) + varint32_len(block_size);
 
     for (uint32_t base = 0; base < num_blocks; base += 1024) {
         const uint32_t i = base + tid;
-        const uint64_t mine = (i < num_blocks) ? (uint64_t)block_bytes[i] : 0;
-        // inclusive scan inside the wave
-        uint64_t x = mine;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, (int)d);
-            const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), (int)d);
-            if (lane >= d) x += ((uint64_t)hi << 32) | lo;
-        }
-        if (lane == 63) wave_sums[wave] = x;
-        __syncthreads();
-        uint64_t before = carry_s;
-        for (uint32_t w = 0; w < wave; ++w) before += wave_sums[w];
-        if (i < num_blocks) offsets[i] = before + x - mine;
-        __syncthreads();
-        if (tid == 1023) carry_s = before + x;
-        __syncthreads();
+        uint64_t total;
+        const uint64_t at = carry + workgroup_exclusive_scan((i < num_blocks) ? (uint64_t)block_bytes[i] : 0, wave_sums, total);
+        if (i < num_blocks) offsets[i] = at;
+        carry += total;
     }
     if (tid == 0) {
-        offsets[num_blocks] = carry_s;
-        if (stream_len) *stream_len = carry_s;
+        offsets[num_blocks] = carry;
+        if (stream_len) *stream_len = carry;
     }
 }
 
@@ -1801,26 +1759,6 @@ __device__ __forceinline__ void predecode_window(uint64_t w, uint32_t pos, uint3
 // Same strictness as the element loop: any invalid element, overrun of the block's output, zero offset or reach before
 // the block start makes the block invalid.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane)
-{
-#ifdef SNAPPY_EMU
-    for (uint32_t d = 1; d < kWave; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)v, (int)d);
-        if (lane >= d) v += t;
-    }
-#else
-    (void)lane;
-    // Hillis-Steele inside each row of 16 lanes (row_shr:1,2,4,8; lanes without a source keep the 0 of `old`), then the row
-    // totals travel up: lane 15 of rows 0 and 2 into rows 1 and 3, lane 31 into rows 2 and 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-#endif
-    return v;
-}
 
 // Follow the element chain of one window: E collects the lanes where an element starts, s ends at or beyond wlim.
 // advv = compressed bytes the element that starts at a lane takes (64 for a start predecode rejected: ends the walk).
@@ -2213,11 +2151,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void decom
 
     // Persistent: wavefronts draw blocks from *next_block (zeroed per launch).
     for (;;) {
-        uint32_t drawn = 0;
-        if (lane == 0) drawn = atomicAdd(next_block, 1u);
-        const uint32_t gb = uni(drawn);
+        const uint32_t gb = draw_work(next_block, lane);
         if (gb >= num_blocks) break;
-        uint32_t c = 0;
+        uint32_t c = 0;              // (batch_container_of, written out: through the function K2's prologue comes out in another order)
         while (c + 1 < w.count && gb >= w.first_block[c + 1]) ++c;
         const uint32_t b = gb - w.first_block[c];
         const uint8_t* __restrict__ stream = w.stream[c];

@@ -3,7 +3,7 @@
 //
 // The blocks of the format are independent, so bytes [offset, offset + length) of a container need only the blocks they
 // touch.  The work unit is a PIECE: a pair (range r, block b) for every block b that range r touches.  Two kernels:
-//   * range_pieces_kernel (one workgroup, in the style of scan_block_bytes_kernel): validates every range, initialises its
+//   * range_pieces_kernel (one workgroup, the planner loop of scan_block_bytes_kernel): validates every range, initialises its
 //     status and writes the exclusive prefix of the ranges' piece counts;
 //   * decompress_ranges_kernel (persistent wavefronts, one counter, as K2): a wavefront draws a piece index, finds its range
 //     by a binary search over the prefix and decodes the block with K2's own decoder (k2_decode_block).  A block wholly
@@ -12,11 +12,11 @@
 // Strict as K2: every touched block is decoded in full, and a range is OK iff every block it touches is.  Nothing outside
 // [dst_r, dst_r + length_r) is written (the slots excepted), whatever the stream holds.
 #pragma once
+#include "snappy_device_common.hpp"
 #include "snappy_kernels.hpp"
 
 namespace snappy_hip {
 
-constexpr uint32_t kRangeOutOfBounds = 2;           // SNAPPY_HIP_RANGE_OUT_OF_BOUNDS
 constexpr uint64_t kMaxRangePieces = 1ull << 31;    // pieces one call decodes at most (the work counter is 32 bits)
 
 struct RangeDesc {             // must match snappy_hip_range (include/snappy_hip.h)
@@ -29,8 +29,8 @@ struct RangeDesc {             // must match snappy_hip_range (include/snappy_hi
 
 // Scratch of one call: the piece prefix (range_count + 2 u64: [r] = first piece of range r, [range_count] = all pieces,
 // [range_count + 1] = pieces to decode), rounded up to 256 bytes, then one slot per wavefront.
-__host__ __device__ inline uint64_t range_prefix_bytes(uint32_t range_count) { return (((uint64_t)range_count + 2u) * 8u + 255u) & ~255ull; }
-__host__ __device__ inline uint64_t range_slot_bytes(uint32_t max_block_size) { return ((uint64_t)max_block_size + 255u) & ~255ull; }
+__host__ __device__ inline uint64_t range_prefix_bytes(uint32_t range_count) { return round256(((uint64_t)range_count + 2u) * 8u); }
+__host__ __device__ inline uint64_t range_slot_bytes(uint32_t max_block_size) { return round256(max_block_size); }
 
 // Pieces of one range, or ~0 for a malformed request: a stream index >= count, offset + length beyond the container (or
 // overflowing), a block size of 0 or above max_block_size (the slot holds no more), an index of too few blocks.
@@ -53,13 +53,10 @@ __global__ __launch_bounds__(1024) void range_pieces_kernel(const StreamDesc* __
                                                             uint64_t* __restrict__ prefix)
 {
     __shared__ uint64_t wave_sums[16];
-    __shared__ uint64_t carry_s;
     __shared__ uint64_t cut_s;      // pieces to decode when there are more than kMaxRangePieces
     const uint32_t tid = threadIdx.x;
-    const uint32_t lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
 
+    uint64_t carry = 0;
     for (uint32_t base = 0; base < range_count; base += 1024) {
         const uint32_t i = base + tid;
         uint64_t mine = 0;
@@ -69,51 +66,23 @@ __global__ __launch_bounds__(1024) void range_pieces_kernel(const StreamDesc* __
             bad = n == ~0ull;
             mine = bad ? 0 : n;
         }
-        // inclusive scan inside the wave, then across the waves (scan_block_bytes_kernel)
-        uint64_t x = mine;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, (int)d);
-            const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), (int)d);
-            if (lane >= d) x += ((uint64_t)hi << 32) | lo;
-        }
-        if (lane == 63) wave_sums[wave] = x;
-        __syncthreads();
-        uint64_t before = carry_s;
-        for (uint32_t w = 0; w < wave; ++w) before += wave_sums[w];
+        uint64_t total;
+        const uint64_t first = carry + workgroup_exclusive_scan(mine, wave_sums, total);
         if (i < range_count) {
-            const uint64_t first = before + x - mine;
             prefix[i] = first;
             // past kMaxRangePieces: the range that straddles it (exactly one when there are more pieces) marks the cut
             const bool beyond = first + mine > kMaxRangePieces;
             if (beyond && first <= kMaxRangePieces) cut_s = first;
             status[i] = (bad || beyond) ? kRangeOutOfBounds : kBlockOk;
         }
-        __syncthreads();
-        if (tid == 1023) carry_s = before + x;
-        __syncthreads();
+        carry += total;
     }
+    __syncthreads();                // (cut_s, whichever trip wrote it)
     if (tid == 0) {
-        prefix[range_count] = carry_s;
-        prefix[range_count + 1] = carry_s > kMaxRangePieces ? cut_s : carry_s;
+        prefix[range_count] = carry;
+        prefix[range_count + 1] = carry > kMaxRangePieces ? cut_s : carry;
     }
 }
-
-// A pointer the kernel reads from a descriptor in memory, not from its arguments, is generic to the compiler, and generic
-// accesses become flat_* instructions -- which K2's decoder must not use (it relies on global_* operations of a wavefront
-// completing in order, tests/test_abi_symbols.py).  Loaded as a pointer to global memory, it keeps that knowledge.
-template <class T>
-__device__ __forceinline__ T* load_global_ptr(T* const* field)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(1))) T* global_t;
-    return (T*)*reinterpret_cast<const global_t*>(reinterpret_cast<uintptr_t>(field));
-#else
-    return *field;
-#endif
-}
-
-// unaligned 16-byte store, the twin of ld128 (snappy_k1_stream.hpp)
-__device__ __forceinline__ void st128(uint8_t* p, uint4 v) { __builtin_memcpy(p, &v, 16); }
 
 __global__ __launch_bounds__(64) void decompress_ranges_kernel(const StreamDesc* __restrict__ descs, const RangeDesc* __restrict__ ranges,
                                                                uint32_t range_count, uint32_t* __restrict__ status,
@@ -127,18 +96,9 @@ __global__ __launch_bounds__(64) void decompress_ranges_kernel(const StreamDesc*
     uint8_t* slot = slots + (uint64_t)blockIdx.x * slot_bytes;
 
     for (;;) {
-        uint32_t drawn = 0;
-        if (lane == 0) drawn = atomicAdd(next_piece, 1u);
-        const uint32_t p = uni(drawn);
+        const uint32_t p = draw_work(next_piece, lane);
         if (p >= pieces) break;
-        // the range: the last r with prefix[r] <= p (ranges of no pieces share their prefix with the next one)
-        uint32_t lo = 0, hi = range_count;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (uld64(reinterpret_cast<const uint8_t*>(prefix + mid)) <= p) lo = mid;
-            else hi = mid;
-        }
-        const uint32_t r = lo;
+        const uint32_t r = prefix_owner<true>(prefix, range_count, p);
         const RangeDesc q = ranges[r];
         const StreamDesc d = descs[q.stream];
         // validated by range_pieces_kernel: offset + length <= total_len < 4 GiB, block_size in [1, max_block_size]
@@ -158,24 +118,13 @@ __global__ __launch_bounds__(64) void decompress_ranges_kernel(const StreamDesc*
             // partial piece: the whole block into this wavefront's slot, then the intersection out
             st = k2_decode_block(stream, d.stream_len, at, slot, out_len, stage);
             if (st == kBlockOk) {
-#ifndef SNAPPY_EMU
-                __builtin_amdgcn_s_waitcnt(0);                           // the decode's stores have landed
-#endif
-                __builtin_amdgcn_wave_barrier();
+                stores_landed();                                         // (the decode's)
                 const uint32_t from = r_begin > ostart ? r_begin : ostart;
                 const uint32_t to = r_end < ostart + out_len ? r_end : ostart + out_len;
                 const uint32_t n = to - from;
                 const uint8_t* s = slot + (from - ostart);
                 uint8_t* t = dst + (from - r_begin);
-                if (n >= 16u) {
-                    // 16 bytes per lane and step, the last step clamped back to end at n (it rewrites bytes with the same values)
-                    for (uint32_t i = 16u * lane; i < n; i += 16u * kWave) {
-                        const uint32_t o = i < n - 16u ? i : n - 16u;
-                        st128(t + o, ld128(s + o));
-                    }
-                } else if (lane < n) {
-                    t[lane] = s[lane];
-                }
+                wave_copy(t, s, n, lane);
             }
         }
         if (st != kBlockOk && lane == 0) atomicOr(status + r, kBlockInvalid);

@@ -17,7 +17,8 @@
 //     raw_gather_kernel (a workgroup per fragment: the payload without its u32 size word, any alignment on both sides).
 //     Item i's output is byte for byte tools/to_raw_snappy.py convert() of the framed stream of the same plaintext.
 #pragma once
-#include "snappy_update.hpp"
+#include "snappy_device_common.hpp"
+#include "snappy_kernels.hpp"   // k2_decode_block, LdsTableWave
 
 namespace snappy_hip {
 
@@ -45,9 +46,7 @@ __global__ __launch_bounds__(64) void raw_decompress_kernel(const RawItem* __res
     const uint32_t lane = threadIdx.x;
 
     for (;;) {
-        uint32_t drawn = 0;
-        if (lane == 0) drawn = atomicAdd(next_item, 1u);
-        const uint32_t i = uni(drawn);
+        const uint32_t i = draw_work(next_item, lane);
         if (i >= count) break;
         const uint8_t* src = load_global_ptr(&items[i].src);
         uint8_t* dst = load_global_ptr(&items[i].dst);
@@ -100,30 +99,11 @@ __host__ __device__ inline RawLayout raw_layout(uint32_t count, uint32_t max_fra
 {
     RawLayout l;
     l.prefix = 256;
-    l.frag_bytes = l.prefix + update_round256(((uint64_t)count + 1u) * 8u);
-    l.place = l.frag_bytes + update_round256((uint64_t)max_fragments * 4u);
-    l.slots = l.place + update_round256((uint64_t)max_fragments * 8u);
-    l.total = l.slots + update_round256((uint64_t)max_fragments * slot_stride);
+    l.frag_bytes = l.prefix + round256(((uint64_t)count + 1u) * 8u);
+    l.place = l.frag_bytes + round256((uint64_t)max_fragments * 4u);
+    l.slots = l.place + round256((uint64_t)max_fragments * 8u);
+    l.total = l.slots + round256((uint64_t)max_fragments * slot_stride);
     return l;
-}
-
-__device__ __forceinline__ uint32_t raw_varint_len(uint32_t v)
-{
-    uint32_t n = 1;
-    while (v >= 0x80u) { v >>= 7; ++n; }
-    return n;
-}
-
-// the item of fragment f: the last i with prefix[i] <= f (items of no fragments share their prefix with the next one)
-__device__ __forceinline__ uint32_t raw_item_of(const uint64_t* __restrict__ prefix, uint32_t count, uint32_t f)
-{
-    uint32_t lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (prefix[mid] <= f) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(1024) void raw_plan_kernel(const RawItem* __restrict__ items, uint32_t count, uint32_t block_size,
@@ -145,7 +125,7 @@ __global__ __launch_bounds__(1024) void raw_plan_kernel(const RawItem* __restric
             else mine = (q.src_len + block_size - 1) / block_size;
         }
         uint64_t total;
-        const uint64_t first = carry + update_scan1024(mine, wave_sums, total);
+        const uint64_t first = carry + workgroup_exclusive_scan(mine, wave_sums, total);
         if (i < count) {
             prefix[i] = first;
             // past max_fragments: the item that straddles it (exactly one when there are more fragments) marks the cut
@@ -155,8 +135,8 @@ __global__ __launch_bounds__(1024) void raw_plan_kernel(const RawItem* __restric
             out_len[i] = 0;
         }
         carry += total;
-        __syncthreads();
     }
+    __syncthreads();                // (cut_s, whichever trip wrote it)
     if (tid == 0) {
         prefix[count] = carry;
         ctl[kRawCtlFragments] = (uint32_t)(carry > max_fragments ? cut_s : carry);
@@ -173,32 +153,22 @@ __global__ __launch_bounds__(64) void raw_compress_fragments_kernel(const RawIte
                                                                     uint32_t* __restrict__ frag_bytes, uint8_t* __restrict__ slots,
                                                                     uint32_t slot_stride, uint32_t* next_fragment)
 {
-    static_assert(kForm == 2 || kForm == 3, "the bulk (2) and the stream (3) form of the parse");
     HIP_DYNAMIC_SHARED(uint8_t, lds_dyn)
-    uint16_t* table = reinterpret_cast<uint16_t*>(lds_dyn);
-    uint8_t* dup_scratch = lds_dyn + 2u * lds_table_entries(block_size);
+    const LdsTableWave k1(lds_dyn, block_size);
     const uint32_t lane = threadIdx.x;
     const uint32_t fragments = uni(ctl[kRawCtlFragments]);
 
     for (;;) {
-        uint32_t drawn = 0;
-        if (lane == 0) drawn = atomicAdd(next_fragment, 1u);
-        const uint32_t f = uni(drawn);
+        const uint32_t f = draw_work(next_fragment, lane);
         if (f >= fragments) break;
-        const uint32_t i = raw_item_of(prefix, count, f);
+        const uint32_t i = prefix_owner<false>(prefix, count, f);
         const uint8_t* src = load_global_ptr(&items[i].src);
         const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));   // (validated: < 4 GiB)
         const uint64_t start = (f - uld64(reinterpret_cast<const uint8_t*>(prefix + i))) * block_size;
         const uint64_t left = src_len - start;
         const uint32_t n = left < block_size ? (uint32_t)left : block_size;
         uint8_t* out = slots + (uint64_t)f * slot_stride;
-        if constexpr (kForm == 3) {
-            SoloMate solo;
-            compress_one_block_stream<LdsTable, kStreamSlotsLds>(src, start, src_len, n, out, LdsTable{table}, lane, frag_bytes + f,
-                                                                 (lds_bytes_t)dup_scratch, solo);
-        } else {
-            compress_one_block_bulk<LdsTable, 64>(src, start, src_len, n, out, LdsTable{table}, lane, frag_bytes + f, (lds_bytes_t)dup_scratch);
-        }
+        LDS_TABLE_WAVE_COMPRESS(kForm, k1, src, start, src_len, n, out, lane, frag_bytes + f);
         __syncthreads();
     }
 }
@@ -214,16 +184,11 @@ __global__ __launch_bounds__(64) void raw_sizes_kernel(const RawItem* __restrict
         if (uni(status[i]) != kBlockOk) continue;
         const uint64_t first = uld64(reinterpret_cast<const uint8_t*>(prefix + i)), end = uld64(reinterpret_cast<const uint8_t*>(prefix + i + 1));
         const uint32_t src_len = (uint32_t)uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));
-        const uint32_t hdr = raw_varint_len(src_len);
-        uint64_t at = hdr;
+        uint64_t at = varint32_len(src_len);
         for (uint64_t base = first; base < end; base += kWave) {
             const uint64_t f = base + lane;
             const uint32_t mine = f < end ? frag_bytes[f] - 4u : 0u;
-            uint32_t x = mine;
-            for (uint32_t d = 1; d < kWave; d <<= 1) {
-                const uint32_t t = (uint32_t)__shfl_up((int)x, (int)d);
-                if (lane >= d) x += t;
-            }
+            const uint32_t x = wave_inclusive_scan(mine, lane);
             if (f < end) place[f] = at + (x - mine);
             at += (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
         }
@@ -234,9 +199,7 @@ __global__ __launch_bounds__(64) void raw_sizes_kernel(const RawItem* __restrict
             if (at > capacity) {
                 status[i] = kRawDstTooSmall;
             } else {
-                uint32_t v = src_len, k = 0;
-                while (v >= 0x80u) { dst[k++] = (uint8_t)(v | 0x80u); v >>= 7; }
-                dst[k] = (uint8_t)v;
+                put_varint32(dst, src_len);
                 atomicAdd(result + 1, 1u);
             }
         }
@@ -244,7 +207,7 @@ __global__ __launch_bounds__(64) void raw_sizes_kernel(const RawItem* __restrict
 }
 
 // One 256-thread workgroup per fragment: frag_bytes[f] - 4 bytes from behind the size word of slot f to the fragment's place
-// in its item's dst; both ends at any alignment.  16-byte stores on the aligned middle of the destination (merge_stream_kernel).
+// in its item's dst; both ends at any alignment (workgroup_copy, as merge_stream_kernel).
 __global__ __launch_bounds__(256) void raw_gather_kernel(const RawItem* __restrict__ items, uint32_t count, const uint32_t* __restrict__ ctl,
                                                          const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ frag_bytes,
                                                          const uint64_t* __restrict__ place, const uint8_t* __restrict__ slots,
@@ -252,19 +215,11 @@ __global__ __launch_bounds__(256) void raw_gather_kernel(const RawItem* __restri
 {
     const uint32_t fragments = ctl[kRawCtlFragments];
     for (uint32_t f = blockIdx.x; f < fragments; f += gridDim.x) {
-        const uint32_t i = raw_item_of(prefix, count, f);
+        const uint32_t i = prefix_owner<false>(prefix, count, f);
         if (status[i] != kBlockOk) continue;
         const uint8_t* src = slots + (uint64_t)f * slot_stride + 4;
         uint8_t* dst = load_global_ptr(&items[i].dst) + place[f];
-        const uint32_t len = frag_bytes[f] - 4u;
-        const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);   // bytes until dst is 16-byte aligned
-        const uint32_t h = head < len ? head : len;
-        if (threadIdx.x < h) dst[threadIdx.x] = src[threadIdx.x];
-        const uint32_t body = (len - h) & ~15u;
-        for (uint32_t k = threadIdx.x * 16; k < body; k += 256 * 16)
-            *reinterpret_cast<uint4*>(dst + h + k) = ld128(src + h + k);
-        const uint32_t done = h + body;
-        if (done + threadIdx.x < len) dst[done + threadIdx.x] = src[done + threadIdx.x];
+        workgroup_copy(dst, src, frag_bytes[f] - 4u);
     }
 }
 

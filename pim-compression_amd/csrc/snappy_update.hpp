@@ -16,7 +16,8 @@
 //     header;
 //   * merge_stream_kernel  (one workgroup per block): copies the block from the old stream or from its compressed slot.
 #pragma once
-#include "snappy_ranges.hpp"
+#include "snappy_device_common.hpp"
+#include "snappy_kernels.hpp"   // StreamDesc, k2_decode_block, LdsTableWave
 
 namespace snappy_hip {
 
@@ -41,20 +42,19 @@ struct UpdateLayout {
     uint64_t span, rank, dirty, dirty_bytes, patch, cslots, total;
     uint32_t patch_slot_bytes, slot_stride;
 };
-__host__ __device__ inline uint64_t update_round256(uint64_t v) { return (v + 255u) & ~255ull; }
 __host__ __device__ inline UpdateLayout update_layout(uint32_t block_size, uint32_t num_blocks, uint32_t max_dirty, uint32_t patch_slots,
                                                       uint32_t slot_stride)
 {
     UpdateLayout l;
-    l.patch_slot_bytes = (uint32_t)update_round256((uint64_t)block_size + kPatchSlack);
+    l.patch_slot_bytes = (uint32_t)round256((uint64_t)block_size + kPatchSlack);
     l.slot_stride = slot_stride;
     l.span = 256;
-    l.rank = l.span + update_round256((uint64_t)num_blocks * 4u);
-    l.dirty = l.rank + update_round256((uint64_t)num_blocks * 4u);
-    l.dirty_bytes = l.dirty + update_round256((uint64_t)max_dirty * 4u);
-    l.patch = l.dirty_bytes + update_round256((uint64_t)max_dirty * 4u);
+    l.rank = l.span + round256((uint64_t)num_blocks * 4u);
+    l.dirty = l.rank + round256((uint64_t)num_blocks * 4u);
+    l.dirty_bytes = l.dirty + round256((uint64_t)max_dirty * 4u);
+    l.patch = l.dirty_bytes + round256((uint64_t)max_dirty * 4u);
     l.cslots = l.patch + (uint64_t)patch_slots * l.patch_slot_bytes;
-    l.total = l.cslots + update_round256((uint64_t)max_dirty * slot_stride);
+    l.total = l.cslots + round256((uint64_t)max_dirty * slot_stride);
     return l;
 }
 
@@ -110,29 +110,6 @@ __global__ __launch_bounds__(256) void update_mark_kernel(const StreamDesc* __re
     span[b] = mine;                  // kNotDirty here = "touched": a span is at most 4 + 2^32 - 1 only when the link is broken
 }
 
-// inclusive scan of one u32 per thread over the 1024 threads of the workgroup; returns the exclusive prefix, `total` =
-// the workgroup's sum.  (scan_block_bytes_kernel's shape.)
-__device__ __forceinline__ uint64_t update_scan1024(uint64_t mine, uint64_t* wave_sums, uint64_t& total)
-{
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t x = mine;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)x, (int)d);
-        const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(x >> 32), (int)d);
-        if (lane >= d) x += ((uint64_t)hi << 32) | lo;
-    }
-    __syncthreads();
-    if (lane == 63) wave_sums[wave] = x;
-    __syncthreads();
-    uint64_t before = 0;
-    total = 0;
-    for (uint32_t w = 0; w < 16; ++w) {
-        if (w < wave) before += wave_sums[w];
-        total += wave_sums[w];
-    }
-    return before + x - mine;
-}
-
 __global__ __launch_bounds__(1024) void update_plan_kernel(const StreamDesc* __restrict__ desc, uint32_t total_len, uint32_t block_size,
                                                            uint32_t num_blocks, const WriteDesc* __restrict__ writes, uint32_t write_count,
                                                            uint32_t* __restrict__ write_status, uint32_t max_dirty,
@@ -166,7 +143,7 @@ __global__ __launch_bounds__(1024) void update_plan_kernel(const StreamDesc* __r
             const uint32_t b = base + tid;
             const bool is_dirty = b < num_blocks && span[b] == kNotDirty;
             uint64_t total;
-            const uint64_t k = carry + update_scan1024(is_dirty ? 1u : 0u, wave_sums, total);
+            const uint64_t k = carry + workgroup_exclusive_scan(is_dirty ? 1u : 0u, wave_sums, total);
             if (b < num_blocks) rank[b] = is_dirty ? (uint32_t)k : kNotDirty;
             if (is_dirty && k < max_dirty) dirty[k] = b;
             carry += total;
@@ -183,20 +160,6 @@ __global__ __launch_bounds__(1024) void update_plan_kernel(const StreamDesc* __r
     }
 }
 
-// n bytes from s to t (any alignment), by the whole wavefront: 16 bytes per lane and step, the last step clamped back to
-// end at n (it rewrites bytes with the same values)
-__device__ __forceinline__ void wave_copy(uint8_t* t, const uint8_t* s, uint32_t n, uint32_t lane)
-{
-    if (n >= 16u) {
-        for (uint32_t i = 16u * lane; i < n; i += 16u * kWave) {
-            const uint32_t o = i < n - 16u ? i : n - 16u;
-            st128(t + o, ld128(s + o));
-        }
-    } else if (lane < n) {
-        t[lane] = s[lane];
-    }
-}
-
 // kForm: the form of K1's parse the LDS-table kernel of the product runs at this block size (3 = stream, 2 = bulk); launched
 // with that kernel's dynamic LDS (lds_table_stream_lds_bytes / lds_table_kernel_lds_bytes)
 template <int kForm>
@@ -207,12 +170,10 @@ __global__ __launch_bounds__(64) void recompress_dirty_kernel(const StreamDesc* 
                                                               uint32_t patch_slot_bytes, uint8_t* __restrict__ cslots, uint32_t slot_stride,
                                                               uint32_t* next_dirty)
 {
-    static_assert(kForm == 2 || kForm == 3, "the bulk (2) and the stream (3) form of the parse");
     __shared__ __attribute__((aligned(16))) uint8_t stage_mem[kK2StageBytes];   // one window's output (K2's stage)
     HIP_DYNAMIC_SHARED(uint8_t, lds_dyn)
     lds_bytes_t stage = (lds_bytes_t)stage_mem;
-    uint16_t* table = reinterpret_cast<uint16_t*>(lds_dyn);
-    uint8_t* dup_scratch = lds_dyn + 2u * lds_table_entries(block_size);
+    const LdsTableWave k1(lds_dyn, block_size);
     const uint32_t lane = threadIdx.x;
     if (uni(ctl[kCtlVerdict]) != kBlockOk) return;
     const uint32_t count = uni(ctl[kCtlDirty]);
@@ -222,9 +183,7 @@ __global__ __launch_bounds__(64) void recompress_dirty_kernel(const StreamDesc* 
     const uint64_t stream_len = uld64(reinterpret_cast<const uint8_t*>(&desc->stream_len));
 
     for (;;) {
-        uint32_t drawn = 0;
-        if (lane == 0) drawn = atomicAdd(next_dirty, 1u);
-        const uint32_t k = uni(drawn);
+        const uint32_t k = draw_work(next_dirty, lane);
         if (k >= count) break;
         const uint32_t b = uni(dirty[k]);
         const uint32_t begin = b * block_size;               // (validated: total_len < 4 GiB)
@@ -242,10 +201,7 @@ __global__ __launch_bounds__(64) void recompress_dirty_kernel(const StreamDesc* 
         uint32_t st = kBlockOk;
         if (covered < n) {
             st = k2_decode_block(stream, stream_len, uld64(reinterpret_cast<const uint8_t*>(offsets + b)), slot, n, stage);
-#ifndef SNAPPY_EMU
-            __builtin_amdgcn_s_waitcnt(0);                   // the decode's stores have landed
-#endif
-            __builtin_amdgcn_wave_barrier();
+            stores_landed();                                 // (the decode's)
         }
         if (st != kBlockOk) {
             if (lane == 0) {
@@ -260,18 +216,9 @@ __global__ __launch_bounds__(64) void recompress_dirty_kernel(const StreamDesc* 
                 const uint32_t from = (uint32_t)(wo > begin ? wo : begin), to = (uint32_t)(we < end ? we : end);
                 if (to > from) wave_copy(slot + (from - begin), load_global_ptr(&writes[i].src) + (from - wo), to - from, lane);
             }
-#ifndef SNAPPY_EMU
-            __builtin_amdgcn_s_waitcnt(0);                   // the patched block is in memory before K1 reads it
-#endif
-            __builtin_amdgcn_wave_barrier();
+            stores_landed();                                 // the patched block is in memory before K1 reads it
             uint8_t* out = cslots + (uint64_t)k * slot_stride;
-            if constexpr (kForm == 3) {
-                SoloMate solo;
-                compress_one_block_stream<LdsTable, kStreamSlotsLds>(slot, 0, n, n, out, LdsTable{table}, lane, dirty_bytes + k,
-                                                                     (lds_bytes_t)dup_scratch, solo);
-            } else {
-                compress_one_block_bulk<LdsTable, 64>(slot, 0, n, n, out, LdsTable{table}, lane, dirty_bytes + k, (lds_bytes_t)dup_scratch);
-            }
+            LDS_TABLE_WAVE_COMPRESS(kForm, k1, slot, 0, n, n, out, lane, dirty_bytes + k);
         }
         __syncthreads();
     }
@@ -295,22 +242,13 @@ __global__ __launch_bounds__(1024) void update_sizes_kernel(uint32_t total_len, 
         }
         return;
     }
-    uint8_t hb[10];
-    uint32_t hdr_len = 0;
-    {
-        uint32_t v = total_len;
-        while (v >= 0x80) { hb[hdr_len++] = (uint8_t)(v | 0x80); v >>= 7; }
-        hb[hdr_len++] = (uint8_t)v;
-        v = block_size;
-        while (v >= 0x80) { hb[hdr_len++] = (uint8_t)(v | 0x80); v >>= 7; }
-        hb[hdr_len++] = (uint8_t)v;
-    }
+    const uint32_t hdr_len = varint32_len(total_len) + varint32_len(block_size);
     auto size_of = [&](uint32_t b) -> uint64_t { return rank[b] == kNotDirty ? span[b] : dirty_bytes[rank[b]]; };
     // first the length alone: a stream that does not fit leaves no byte behind
     uint64_t mine = 0;
     for (uint32_t b = tid; b < num_blocks; b += 1024) mine += size_of(b);
     uint64_t new_len;
-    (void)update_scan1024(mine, wave_sums, new_len);
+    (void)workgroup_exclusive_scan(mine, wave_sums, new_len);
     new_len += hdr_len;
     if (new_len > capacity) {
         if (tid == 0) {
@@ -324,12 +262,12 @@ __global__ __launch_bounds__(1024) void update_sizes_kernel(uint32_t total_len, 
     for (uint32_t base = 0; base < num_blocks; base += 1024) {
         const uint32_t b = base + tid;
         uint64_t total;
-        const uint64_t at = carry + update_scan1024(b < num_blocks ? size_of(b) : 0u, wave_sums, total);
+        const uint64_t at = carry + workgroup_exclusive_scan(b < num_blocks ? size_of(b) : 0u, wave_sums, total);
         if (b < num_blocks) new_offsets[b] = at;
         carry += total;
     }
     if (tid == 0) {
-        for (uint32_t i = 0; i < hdr_len; ++i) new_stream[i] = hb[i];
+        put_varint32(new_stream + put_varint32(new_stream, total_len), block_size);
         new_offsets[num_blocks] = carry;
         *new_stream_len = carry;
         result[0] = kBlockOk;
@@ -339,8 +277,7 @@ __global__ __launch_bounds__(1024) void update_sizes_kernel(uint32_t total_len, 
 }
 
 // One 256-thread workgroup per block: new_offsets[b + 1] - new_offsets[b] bytes from the old stream (a clean block) or from
-// the block's compressed slot to new_stream + new_offsets[b]; both ends at any alignment.  16-byte stores on the aligned
-// middle of the destination.
+// the block's compressed slot to new_stream + new_offsets[b]; both ends at any alignment (workgroup_copy).
 __global__ __launch_bounds__(256) void merge_stream_kernel(const StreamDesc* __restrict__ desc, uint32_t num_blocks,
                                                            const uint32_t* __restrict__ ctl, const uint32_t* __restrict__ rank,
                                                            const uint8_t* __restrict__ cslots, uint32_t slot_stride,
@@ -353,16 +290,7 @@ __global__ __launch_bounds__(256) void merge_stream_kernel(const StreamDesc* __r
         const uint32_t k = rank[b];
         const uint8_t* src = k == kNotDirty ? old_stream + old_offsets[b] : cslots + (uint64_t)k * slot_stride;
         const uint64_t at = new_offsets[b];
-        uint8_t* dst = new_stream + at;
-        const uint32_t len = (uint32_t)(new_offsets[b + 1] - at);
-        const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);   // bytes until dst is 16-byte aligned
-        const uint32_t h = head < len ? head : len;
-        if (threadIdx.x < h) dst[threadIdx.x] = src[threadIdx.x];
-        const uint32_t body = (len - h) & ~15u;
-        for (uint32_t i = threadIdx.x * 16; i < body; i += 256 * 16)
-            *reinterpret_cast<uint4*>(dst + h + i) = ld128(src + h + i);
-        const uint32_t done = h + body;
-        if (done + threadIdx.x < len) dst[done + threadIdx.x] = src[done + threadIdx.x];
+        workgroup_copy(new_stream + at, src, (uint32_t)(new_offsets[b + 1] - at));
     }
 }
 

@@ -18,8 +18,7 @@ def lib():
         out = os.path.join(HERE, "emu", "libsnappy_emu_raw.so")
         csrc = os.path.join(ROOT, "pim-compression_amd", "csrc")
         deps = [src, os.path.join(HERE, "emu", "emu_runtime.cpp"), os.path.join(HERE, "emu", "hip", "hip_runtime.h")] + \
-            [os.path.join(csrc, f) for f in ("snappy_kernels.hpp", "snappy_k1_stream.hpp", "snappy_ranges.hpp", "snappy_update.hpp",
-                                             "snappy_raw.hpp")] + \
+            [os.path.join(csrc, f) for f in ("snappy_device_common.hpp", "snappy_kernels.hpp", "snappy_k1_stream.hpp", "snappy_raw.hpp")] + \
             [os.path.join(csrc, "ablation", f) for f in os.listdir(os.path.join(csrc, "ablation"))]
         if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
             tmp = out + f".{os.getpid()}.tmp"

@@ -282,6 +282,17 @@ def test_unaligned_and_odd_block_sizes(shb):
         assert st == 0 and out == data, bs
 
 
+@pytest.mark.parametrize("blocks", [1023, 1024, 1025, 2049])
+def test_compact_around_the_planner_trip(shb, blocks):
+    """scan_block_bytes_kernel scans 1024 block sizes per trip of its loop: one block less than a trip, a whole trip, one block
+    and a whole trip more than one (64-byte blocks, the last one of 63 bytes)."""
+    data = golden_bytes("world192.txt")[:blocks * 64 - 1]
+    ref = oracle.compress(data, 64)
+    assert gpu_compress(shb, data, 64) == ref
+    st, out = gpu_decompress(shb, ref)
+    assert st == 0 and out == data
+
+
 def test_decoder_strictness(shb):
     body = bytes([0x00, 0x41, (3 << 2) | 2, 9, 0])                      # offset before block start
     s1 = bytes([5, 0x80, 0x80, 0x02]) + len(body).to_bytes(4, "little") + body

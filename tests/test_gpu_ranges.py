@@ -107,6 +107,16 @@ def test_gpu_ranges_adjacent_rebuild_the_plaintext(shb):
     assert rc.check_buffer(buf, [(29, c.total, c.plain)]) == []
 
 
+def test_gpu_ranges_one_more_than_a_planner_trip(shb):
+    """range_pieces_kernel takes 1024 ranges per trip of its loop: 1025 ranges over a 64 KiB container, so the last range's
+    pieces start at the carry of the first trip.  Ranges of no pieces (length 0) sit among the others."""
+    c = rc.Container(golden_bytes("world192.txt")[:65536], block_size=4096)
+    rng = np.random.default_rng(1025)
+    reqs = [(0, int(o), int(min(c.total - o, n)) * (i % 5 != 0)) for i, (o, n) in enumerate(zip(rng.integers(0, c.total, 1025), rng.integers(1, 9000, 1025)))]
+    assert len(reqs) == 1025 and reqs[1024][2] > 0
+    check_ok(shb, [c], reqs)
+
+
 def test_gpu_ranges_out_of_bounds_damage_and_arguments(shb):
     import torch
     c = rc.Container(golden_bytes("terror2.txt"), block_size=4096)

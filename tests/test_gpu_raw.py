@@ -188,6 +188,21 @@ def test_gpu_raw_compress_items_around_a_fragment(shb, bs, monkeypatch):
         assert d.status[i] == rc.OK and d.window(i) == p, i
 
 
+def test_gpu_raw_compress_one_item_more_than_a_planner_trip(shb):
+    """raw_plan_kernel takes 1024 items per trip of its loop: 1025 items of one fragment each, so the last item's fragment is
+    numbered from the carry of the first trip."""
+    bs = 1000
+    text = golden_bytes("plrabn12.txt")
+    plains = [text[37 * k:37 * k + 1 + (k * 7919) % bs] for k in range(1025)]
+    assert all(0 < len(p) <= bs for p in plains) and len(plains[1024]) > 1
+    wants = [want_raw(p, bs) for p in plains]
+    caps = [len(w) + k % 3 for k, w in enumerate(wants)]
+    b = gpu_compress(shb, list(zip(plains, caps)), bs, 1025)
+    for i, w in enumerate(wants):
+        assert check_compressed(b, i, w, caps[i]), i
+    assert b.result == [1025, 1025]
+
+
 def test_gpu_raw_compress_goldens_bad_items_and_arguments(shb):
     import torch
     names = ["alice", "coding", "terror2", "plrabn12", "world192"]

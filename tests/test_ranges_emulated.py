@@ -25,7 +25,8 @@ def emu_lib():
         out = os.path.join(HERE, "emu", "libsnappy_emu_ranges.so")
         csrc = os.path.join(ROOT, "pim-compression_amd", "csrc")
         deps = [src, os.path.join(HERE, "emu", "emu_runtime.cpp"), os.path.join(HERE, "emu", "hip", "hip_runtime.h"),
-                os.path.join(csrc, "snappy_kernels.hpp"), os.path.join(csrc, "snappy_k1_stream.hpp"), os.path.join(csrc, "snappy_ranges.hpp")] + \
+                os.path.join(csrc, "snappy_device_common.hpp"), os.path.join(csrc, "snappy_kernels.hpp"),
+                os.path.join(csrc, "snappy_k1_stream.hpp"), os.path.join(csrc, "snappy_ranges.hpp")] + \
             [os.path.join(csrc, "ablation", f) for f in os.listdir(os.path.join(csrc, "ablation"))]
         if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
             tmp = out + f".{os.getpid()}.tmp"
