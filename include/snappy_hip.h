@@ -304,7 +304,7 @@ SNAPPY_HIP_API int snappy_hip_decompress_ranges(const snappy_hip_stream_desc *d_
  * `u32 size + elements` are copied as they are.  Blocks are independent and K1 is bit-identical to the reference per block,
  * so for a container this library, the reference or any compressor with the reference's per-block output produced,
  *     the new stream == the compressor's output for the plaintext with the writes applied, byte for byte.
- * Overwrites only: total_len, block_size and the number of blocks do not change.
+ * Overwrites only: total_len, block_size and the number of blocks do not change (snappy_hip_resize below changes the length).
  *
  * d_desc: device, ONE snappy_hip_stream_desc as snappy_hip_decompress_ranges reads it (stream, stream_len, block_offsets of
  *   num_blocks entries, total_len, block_size, num_blocks; result is not read).  total_len and block_size are the host's
@@ -366,6 +366,78 @@ SNAPPY_HIP_API int snappy_hip_update_ranges(const snappy_hip_stream_desc *d_desc
                              uint8_t *d_new_stream, uint64_t new_stream_capacity, uint64_t *d_new_offsets,
                              uint64_t *d_new_stream_len, uint32_t *d_result, uint32_t max_dirty_blocks, void *d_scratch,
                              uint64_t scratch_bytes, void *stream);
+
+/*
+ * ONE framed container grown and shrunk in place: truncate (no segments), append (keep_len == total_len), or "rewrite from
+ * here on" (both).  The new plaintext is the first keep_len bytes of the old one followed by the bytes of the segments in
+ * order.  Every block wholly in front of keep_len ("kept": blocks 0 .. keep_len / block_size - 1) is copied as it is; the
+ * block keep_len cuts (when keep_len % block_size != 0) is decoded (K2's decoder) and, with every block behind it up to the
+ * new last one, compressed (K1, LDS-table form).  Blocks are independent and K1 is bit-identical to the reference per block,
+ * so for a container this library, the reference or any compressor with the reference's per-block output produced,
+ *     the new stream == the compressor's output for plaintext[0, keep_len) + the segments' bytes, byte for byte
+ * -- the header has the new length (so a kept block's new offset need not be its old one) and the last block is compressed
+ * at its new length (K1 sizes its hash table by it, as the reference does, snappy_compress.c:139-146).
+ *
+ * d_desc: device, ONE snappy_hip_stream_desc as snappy_hip_update_ranges reads it (stream, stream_len, block_offsets of
+ *   num_blocks entries, total_len, block_size, num_blocks; result is not read).  total_len, block_size, keep_len and
+ *   new_total_len are the host's copies: they size the launches.  The device checks that the descriptor's total_len,
+ *   block_size and num_blocks are the host's, that keep_len <= total_len, and that keep_len + the sum of the segments'
+ *   lengths (in 64 bits) == new_total_len.
+ * d_segments, d_segment_status: device arrays of segment_count entries, so that segments can be produced on the device.  A
+ *   segment of length 0 is allowed (its src may be null) and brings nothing.
+ * d_new_stream (new_stream_capacity bytes): the header, then every block in order.  d_new_offsets (new_num_blocks + 1
+ *   entries, new_num_blocks = snappy_hip_num_blocks(new_total_len, block_size), as snappy_hip_compact leaves them): [b] =
+ *   offset of block b's size prefix, [new_num_blocks] = *d_new_stream_len = the new length.  The old stream is never written;
+ *   d_new_stream must not overlap it, the sources or the scratch.
+ * d_segment_status[i] (always written):
+ *   SNAPPY_HIP_BLOCK_OK             the segment is well-formed;
+ *   SNAPPY_HIP_RANGE_OUT_OF_BOUNDS  a null src with length > 0.
+ * d_result[0] (always written):
+ *   SNAPPY_HIP_BLOCK_OK             done.  d_result[1] = the number of blocks that were compressed.
+ *   SNAPPY_HIP_UPDATE_REJECTED      all or nothing: some segment is not OK, or keep_len + the lengths is not new_total_len
+ *                                   (a length of 2^32 or more never is), or keep_len > total_len, or the descriptor's total_len
+ *                                   / block_size / num_blocks are not the host's (d_result[1] = 0 for all of these), or the new
+ *                                   length exceeds new_stream_capacity (d_result[1] = the blocks that were compressed).
+ *                                   *d_new_stream_len = 0 and NOT ONE BYTE of d_new_stream or d_new_offsets is written.  The
+ *                                   later kernels read the verdict from device memory and leave; the host is not asked.
+ *   SNAPPY_HIP_BLOCK_INVALID        the container itself is bad: a kept block whose chain link does not hold (offsets[b] + 4 +
+ *                                   le32(stream + offsets[b]) == offsets[b + 1], the last one against stream_len: the rule of
+ *                                   snappy_hip_verify_index, so a copy never reads outside the stream), or a cut block that
+ *                                   does not decode under the strictness of snappy_hip_decompress_blocks (it is decoded in
+ *                                   full, not only its first keep_len % block_size bytes).  d_result[1] = the number of
+ *                                   blocks that were compressed; *d_new_stream_len = 0; the contents of d_new_stream /
+ *                                   d_new_offsets are unspecified; the old stream is intact.
+ *   Blocks wholly behind keep_len are never read: damage there cannot matter.  With keep_len on a block boundary nothing is
+ *   decoded at all.  A kept block is copied, NOT decoded: damage inside its payload with an intact link travels along.
+ *   keep_len == total_len without segments gives the stream again (chain checked, a short last block decoded and compressed
+ *   again); new_total_len == 0 gives the header.
+ *
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_resize_scratch_bytes(...) bytes for the same
+ * block_size, new_total_len, keep_len and segment_count on the current device (old_num_blocks sizes nothing today), not shared
+ * with a launch that runs concurrently; contents need not be initialised.  It holds one u64 per segment, two u32 per block of
+ * the new container, a u32 and one compressed slot (snappy_hip_slot_stride) per compressed block, and one patch slot
+ * (block_size + 64 bytes, rounded up to 256) per wavefront of the recompress kernel, as in snappy_hip_update_ranges.
+ * The call only enqueues work on `stream`; it never synchronises and never calls the allocator.  A resize can follow an
+ * update or another resize (and the other way round): d_new_stream / d_new_offsets go into the next descriptor, with an 8-byte
+ * device copy of *d_new_stream_len into its stream_len.
+ * SNAPPY_HIP_ERR_ARG (host side): null pointers, a bad block size, a scratch that is too small or misaligned.  (A new
+ * length that does not fit the format's 32 bits cannot be passed: new_total_len is a uint32_t.  The drop-in call below and
+ * the Python binding refuse it.)
+ * The compressed blocks go through K1's LDS-table form only -- few wavefronts per CU -- as the update's dirty blocks do.  A
+ * caller that appends gigabytes should compress the new data with snappy_hip_compress_blocks instead; DESIGN.md 3.7 is where
+ * the measured crossover belongs.
+ */
+typedef struct snappy_hip_segment {
+	const void *src;      /* device: length bytes, any alignment                 */
+	uint64_t length;      /* bytes                                               */
+} snappy_hip_segment;
+SNAPPY_HIP_API uint64_t snappy_hip_resize_scratch_bytes(uint32_t block_size, uint32_t old_num_blocks, uint32_t new_total_len, uint32_t keep_len,
+                                         uint32_t segment_count);
+SNAPPY_HIP_API int snappy_hip_resize(const snappy_hip_stream_desc *d_desc, uint32_t total_len, uint32_t block_size,
+                      uint32_t keep_len, uint32_t new_total_len,
+                      const snappy_hip_segment *d_segments, uint32_t segment_count, uint32_t *d_segment_status,
+                      uint8_t *d_new_stream, uint64_t new_stream_capacity, uint64_t *d_new_offsets,
+                      uint64_t *d_new_stream_len, uint32_t *d_result, void *d_scratch, uint64_t scratch_bytes, void *stream);
 
 /* ---- 1a. batches of raw Snappy streams, described on the device ---------- */
 
@@ -473,6 +545,19 @@ SNAPPY_HIP_API snappy_status snappy_decompress_range_gpu(struct host_buffer_cont
  */
 SNAPPY_HIP_API snappy_status snappy_update_range_gpu(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
                                       struct host_buffer_context *output, struct program_runtime *runtime);
+
+/*
+ * The framed stream in input with its plaintext cut to its first keep_len bytes and tail->buffer[0, tail->length) appended,
+ * written to output (as in snappy_compress_gpu: realloc'd to the new size, or used as is when output->max is finite,
+ * SNAPPY_BUFFER_TOO_SMALL if the new stream does not fit).  tail may be NULL or empty: a truncate.  Parses the header and
+ * walks the whole u32 size chain on the host, copies the stream and the tail to the current device, runs one
+ * snappy_hip_resize there (one segment; only the block keep_len cuts is decoded, only it and the blocks behind it are
+ * compressed) and copies the new stream back.  The result is byte for byte what snappy_compress_gpu gives for the new
+ * plaintext.  SNAPPY_INVALID_INPUT: a malformed header or chain, keep_len beyond the uncompressed length, a new length that
+ * does not fit the format's 32 bits, or a cut block that does not decode.  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_resize_gpu(struct host_buffer_context *input, uint64_t keep_len, struct host_buffer_context *tail,
+                                struct host_buffer_context *output, struct program_runtime *runtime);
 
 /* ---- 1c. drop-in level: one buffer of the raw Snappy format -------------- */
 

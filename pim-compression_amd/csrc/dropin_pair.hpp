@@ -883,6 +883,74 @@ snappy_status update_range_gpu_body(struct host_buffer_context* input, struct ho
     return SNAPPY_OK;
 }
 
+// One resize of a framed file (snappy_resize_gpu): the header and the whole size chain on the host (in parallel shares where
+// the stream is long enough, csrc/host_chain.hpp), the whole stream and the tail to the device, one segment through
+// snappy_hip_resize, the new stream back.  `output` is left alone until it succeeds.
+snappy_status resize_gpu_body(struct host_buffer_context* input, uint64_t keep_len, struct host_buffer_context* tail,
+                              struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    if (!input || !output || !runtime || !input->buffer || (tail && tail->length && !tail->buffer)) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length, length = tail ? tail->length : 0;
+    const dropin_plan::Container c = dropin_plan::open_container(buf, in_total);
+    if (!c.hdr) return say(c.bad);
+    if (keep_len > c.total) return say(dropin_plan::refuse("keep length %lu lies beyond the %u uncompressed bytes", (unsigned long)keep_len, c.total));
+    if (length > 0xffffffffull - keep_len)
+        return say(dropin_plan::refuse("%lu + %lu bytes do not fit the format's 32-bit length", (unsigned long)keep_len, (unsigned long)length));
+    if (!block_size_ok(c.bs)) return say(dropin_plan::bad_block_size(c.bs, " in the stream"));
+    const uint64_t nb = c.nb;
+    std::vector<uint64_t> off;
+    const unsigned walk_threads = (unsigned)std::max(1, env_int("SNAPPY_HIP_HOST_WALK_THREADS",
+                                                               (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
+    if (!host_chain::parallel_walk(buf, in_total, c.hdr, nb, c.bs, walk_threads, off))
+        if (const dropin_plan::Verdict v = dropin_plan::walk_to(buf, in_total, c, nb, true, off)) return say(v);
+    if (snappy_status st = call.need_device()) return st;
+    const uint32_t keep = (uint32_t)keep_len, new_total = (uint32_t)(keep_len + length);
+    const uint64_t new_nb = snappy_hip_num_blocks(new_total, c.bs), kept = keep / c.bs;
+    // a kept block keeps its size, a compressed one grows to a slot at most
+    const uint64_t capacity = 16 + (kept ? off[kept] : 0) + (new_nb - kept) * snappy_hip_slot_stride(c.bs);
+    const uint64_t scratch_bytes = snappy_hip_resize_scratch_bytes(c.bs, (uint32_t)nb, new_total, keep, 1);
+
+    uint8_t *d_stream = nullptr, *d_new = nullptr, *d_scratch = nullptr, *d_tail = nullptr;
+    uint64_t *d_boff = nullptr, *d_noff = nullptr;      // d_noff: the new offsets, then the new length
+    snappy_hip_stream_desc* d_desc = nullptr;
+    snappy_hip_segment* d_segment = nullptr;
+    uint32_t* d_words = nullptr;                        // [0] the segment's status, [1..2] the result
+    if (snappy_status st = call.buffers({{&d_stream, in_total}, {&d_boff, (nb + 1) * sizeof(uint64_t)}, {&d_noff, (new_nb + 2) * sizeof(uint64_t)},
+                                         {&d_desc, sizeof *d_desc}, {&d_segment, sizeof *d_segment}, {&d_words, 4 * sizeof(uint32_t)},
+                                         {&d_tail, length}, {&d_new, capacity}, {&d_scratch, scratch_bytes}}))
+        return st;
+    const snappy_hip_stream_desc desc{d_stream, in_total, d_boff, nullptr, c.total, c.bs, c.hdr, (uint32_t)nb};
+    const snappy_hip_segment segment{d_tail, length};
+    if (snappy_status st = call.upload({{d_stream, buf, in_total}, {d_boff, off.data(), (nb + 1) * sizeof(uint64_t)}, {d_desc, &desc, sizeof desc},
+                                        {d_segment, &segment, sizeof segment}, {d_tail, tail ? tail->buffer : nullptr, length}}))
+        return st;
+    if (snappy_status st = call.launch("resize", [&] {
+            return snappy_hip_resize(d_desc, c.total, c.bs, keep, new_total, d_segment, 1, d_words, d_new, capacity, d_noff, d_noff + new_nb + 1,
+                                     d_words + 1, d_scratch, scratch_bytes, nullptr);
+        }))
+        return st;
+    uint32_t words[3] = {0xffffffffu, 0xffffffffu, 0};
+    uint64_t new_len = 0;
+    snappy_status verdict = SNAPPY_OK;
+    if (snappy_status st = call.copy_out([&]() -> int {
+            if (int rc = call.download({{words, d_words, sizeof words}, {&new_len, d_noff + new_nb + 1, sizeof new_len}})) return rc;
+            if (words[0] != SNAPPY_HIP_BLOCK_OK || words[1] != SNAPPY_HIP_BLOCK_OK || new_len > capacity) {
+                fprintf(stderr, "snappy_hip: the stream cannot be resized (segment status %u, result %u)\n", words[0], words[1]);
+                verdict = SNAPPY_INVALID_INPUT;
+                return 0;
+            }
+            if ((verdict = claim_output(output, new_len))) return 0;
+            return call.download({{output->buffer, d_new, new_len}});
+        }))
+        return st;
+    if (verdict) return verdict;
+    if (snappy_status st = call.free_buffers()) return st;
+    place(output, new_len);
+    return SNAPPY_OK;
+}
+
 // The raw ("original") Snappy format, one buffer each way: one item through the batch calls of snappy_raw.hpp.
 struct RawVerdict {            // what one item's call leaves on the device
     uint64_t out_len;
@@ -1002,6 +1070,12 @@ snappy_status snappy_update_range_gpu(struct host_buffer_context* input, struct 
                                       struct host_buffer_context* output, struct program_runtime* runtime)
 {
     return entry_guard([&] { return update_range_gpu_body(input, patch, offset, output, runtime); });
+}
+
+snappy_status snappy_resize_gpu(struct host_buffer_context* input, uint64_t keep_len, struct host_buffer_context* tail,
+                                struct host_buffer_context* output, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return resize_gpu_body(input, keep_len, tail, output, runtime); });
 }
 
 snappy_status snappy_compress_raw_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,

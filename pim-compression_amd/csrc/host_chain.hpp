@@ -83,36 +83,52 @@ inline bool parallel_walk(const uint8_t* buf, uint64_t len, uint64_t first, uint
     for (auto& l : looked) l.store(0, std::memory_order_relaxed);
     std::vector<std::vector<uint64_t>> hops(shares);
     std::vector<char> ok(shares, 1);
+    // A share whose thread cannot be started (std::system_error: the process is at its thread limit) or whose walk throws
+    // (std::bad_alloc from its hop list) fails the whole walk -- the caller then walks serially -- and is marked as having
+    // looked, so that the shares in front of it do not wait for a thread that never ran.
+    bool started_all = true;
     {
         std::vector<std::thread> th;
-        for (uint64_t k = 0; k < shares; ++k)
-            th.emplace_back([&, k] {
-                anchor[k] = k == 0 ? first : find_anchor(buf, len, first, maxc, first + body * k / shares, first + body * (k + 1) / shares);
-                looked[k].store(1, std::memory_order_release);
-                if (anchor[k] == kNone) return;                   // no walker: the one before it walks through this share
-                uint64_t next = len;
-                for (uint64_t j = k + 1; j < shares; ++j) {
-                    while (!looked[j].load(std::memory_order_acquire)) std::this_thread::yield();
-                    if (anchor[j] != kNone) {
-                        next = anchor[j];
-                        break;
-                    }
-                }
-                std::vector<uint64_t>& h = hops[k];
-                h.reserve((size_t)(num_blocks / shares + 64));
-                uint64_t at = anchor[k];
-                while (at < next) {
-                    if (at + 4 > len || h.size() > num_blocks) {
+        try {
+            th.reserve(shares);
+            for (uint64_t k = 0; k < shares; ++k)
+                th.emplace_back([&, k] {
+                    try {
+                        anchor[k] = k == 0 ? first : find_anchor(buf, len, first, maxc, first + body * k / shares, first + body * (k + 1) / shares);
+                        looked[k].store(1, std::memory_order_release);
+                        if (anchor[k] == kNone) return;               // no walker: the one before it walks through this share
+                        uint64_t next = len;
+                        for (uint64_t j = k + 1; j < shares; ++j) {
+                            while (!looked[j].load(std::memory_order_acquire)) std::this_thread::yield();
+                            if (anchor[j] != kNone) {
+                                next = anchor[j];
+                                break;
+                            }
+                        }
+                        std::vector<uint64_t>& h = hops[k];
+                        h.reserve((size_t)(num_blocks / shares + 64));
+                        uint64_t at = anchor[k];
+                        while (at < next) {
+                            if (at + 4 > len || h.size() > num_blocks) {
+                                ok[k] = 0;
+                                return;
+                            }
+                            h.push_back(at);
+                            at += 4 + (uint64_t)le32(buf + at);
+                        }
+                        if (at != next) ok[k] = 0;
+                    } catch (...) {
                         ok[k] = 0;
-                        return;
+                        looked[k].store(1, std::memory_order_release);
                     }
-                    h.push_back(at);
-                    at += 4 + (uint64_t)le32(buf + at);
-                }
-                if (at != next) ok[k] = 0;
-            });
+                });
+        } catch (...) {
+            started_all = false;
+        }
+        for (uint64_t k = th.size(); k < shares; ++k) looked[k].store(1, std::memory_order_release);   // (anchor kNone: never started)
         for (auto& t : th) t.join();
     }
+    if (!started_all) return false;
     uint64_t total = 0;
     for (uint64_t k = 0; k < shares; ++k) {
         if (!ok[k]) return false;

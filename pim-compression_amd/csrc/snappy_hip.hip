@@ -29,6 +29,7 @@
 #include "snappy_ranges.hpp"
 #include "snappy_update.hpp"
 #include "snappy_raw.hpp"
+#include "snappy_resize.hpp"
 
 namespace {
 
@@ -946,6 +947,83 @@ int snappy_hip_update_ranges(const snappy_hip_stream_desc* d_desc, uint32_t tota
     if (nb)
         hipLaunchKernelGGL(snappy_hip::merge_stream_kernel, dim3(nb), dim3(256), 0, st, desc, nb, ctl, rank, scratch + l.cslots, stride,
                            d_new_offsets, d_new_stream);
+    HIP_TRY(hipGetLastError());
+    return SNAPPY_HIP_OK;
+}
+
+// ---- growing and shrinking a container (snappy_resize.hpp) ----
+// the shape of one resize: blocks of the new container, those of them that are compressed, wavefronts of the recompress kernel
+struct ResizeShape {
+    uint32_t new_blocks, compressed, waves;
+};
+static ResizeShape resize_shape(uint32_t block_size, uint32_t new_total_len, uint32_t keep_len)
+{
+    ResizeShape s;
+    s.new_blocks = (uint32_t)snappy_hip_num_blocks(new_total_len, block_size);
+    const uint32_t kept = keep_len / block_size;
+    s.compressed = s.new_blocks > kept ? s.new_blocks - kept : 0;      // (keep_len > new_total_len is REJECTED on the device)
+    s.waves = std::max(1u, std::min(update_grid_cap(block_size), s.compressed));
+    return s;
+}
+
+uint64_t snappy_hip_resize_scratch_bytes(uint32_t block_size, uint32_t old_num_blocks, uint32_t new_total_len, uint32_t keep_len,
+                                         uint32_t segment_count)
+{
+    (void)old_num_blocks;   // (a kept block is a block of the new container too: nothing is sized by the old count)
+    if (!block_size_ok(block_size)) return 0;
+    const ResizeShape s = resize_shape(block_size, new_total_len, keep_len);
+    return snappy_hip::resize_layout(block_size, s.new_blocks, s.compressed, segment_count, s.waves, snappy_hip_slot_stride(block_size)).total;
+}
+
+int snappy_hip_resize(const snappy_hip_stream_desc* d_desc, uint32_t total_len, uint32_t block_size, uint32_t keep_len, uint32_t new_total_len,
+                      const snappy_hip_segment* d_segments, uint32_t segment_count, uint32_t* d_segment_status, uint8_t* d_new_stream,
+                      uint64_t new_stream_capacity, uint64_t* d_new_offsets, uint64_t* d_new_stream_len, uint32_t* d_result, void* d_scratch,
+                      uint64_t scratch_bytes, void* stream)
+{
+    static_assert(sizeof(snappy_hip_segment) == sizeof(snappy_hip::SegmentDesc) && sizeof(snappy_hip::SegmentDesc) == 16, "snappy_hip_segment layout");
+    if (!block_size_ok(block_size)) return fail(SNAPPY_HIP_ERR_ARG, "block_size must be 1..65535");
+    if (!d_desc || !d_new_stream || !d_new_offsets || !d_new_stream_len || !d_result || (segment_count && (!d_segments || !d_segment_status)))
+        return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    const uint32_t nb = (uint32_t)snappy_hip_num_blocks(total_len, block_size);
+    const uint32_t stride = snappy_hip_slot_stride(block_size);
+    const ResizeShape s = resize_shape(block_size, new_total_len, keep_len);
+    const snappy_hip::ResizeLayout l = snappy_hip::resize_layout(block_size, s.new_blocks, s.compressed, segment_count, s.waves, stride);
+    if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_resize_scratch_bytes)");
+    if (int rc = check_knobs()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
+    uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.prefix);
+    uint32_t* span = reinterpret_cast<uint32_t*>(scratch + l.span);
+    uint32_t* rank = reinterpret_cast<uint32_t*>(scratch + l.rank);
+    uint32_t* new_bytes = reinterpret_cast<uint32_t*>(scratch + l.new_bytes);
+    const auto* desc = reinterpret_cast<const snappy_hip::StreamDesc*>(d_desc);
+    const auto* segments = reinterpret_cast<const snappy_hip::SegmentDesc*>(d_segments);
+    HIP_TRY(hipMemsetAsync(ctl, 0, 256, st));
+    if (s.new_blocks)
+        hipLaunchKernelGGL(snappy_hip::resize_mark_kernel, dim3((uint32_t)(((uint64_t)s.new_blocks + 255) / 256)), dim3(256), 0, st, desc, total_len,
+                           block_size, nb, keep_len, s.new_blocks, ctl, span, rank);
+    hipLaunchKernelGGL(snappy_hip::resize_plan_kernel, dim3(1), dim3(1024), 0, st, desc, total_len, block_size, nb, keep_len, new_total_len,
+                       s.new_blocks, segments, segment_count, d_segment_status, ctl, prefix, d_new_stream_len, d_result);
+    HIP_TRY(hipGetLastError());
+    if (s.compressed) {
+        const int rc = launch_counted(st, [&](uint32_t* counter) {
+            with_lds_table_form(block_size, [&](auto form, uint32_t lds) {
+                hipLaunchKernelGGL(snappy_hip::resize_recompress_kernel<form()>, dim3(s.waves), dim3(64), lds, st, desc, total_len, block_size, keep_len,
+                                   new_total_len, segments, segment_count, prefix, ctl, new_bytes, scratch + l.patch, l.patch_slot_bytes,
+                                   scratch + l.cslots, stride, counter);
+            });
+            return 0;
+        });
+        if (rc) return rc;
+    }
+    // a kept block is the update's clean block, new block kept + k its dirty block k: the same sizes, scan, header and merge
+    hipLaunchKernelGGL(snappy_hip::update_sizes_kernel, dim3(1), dim3(1024), 0, st, new_total_len, block_size, s.new_blocks, ctl, span, rank,
+                       new_bytes, d_new_stream, new_stream_capacity, d_new_offsets, d_new_stream_len, d_result);
+    if (s.new_blocks)
+        hipLaunchKernelGGL(snappy_hip::merge_stream_kernel, dim3(std::min(s.new_blocks, 0x7fffffffu)), dim3(256), 0, st, desc, s.new_blocks, ctl, rank,
+                           scratch + l.cslots, stride, d_new_offsets, d_new_stream);
     HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
 }

@@ -5,7 +5,7 @@
  * snappy_decompress_dpu (dpu_snappy.c:169-172, :189-192).  Without -d the host CPU codec runs,
  * as in the reference.  -d never falls back to the CPU.
  *
- *   dpu_snappy [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
  */
 #include <getopt.h>
 #include <limits.h>
@@ -22,7 +22,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "**DEBUG BUILD**\n");
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
-	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
@@ -30,6 +30,8 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
 	fprintf(stderr, "r: decompress only <length> bytes from uncompressed byte <offset> of the input\n");
 	fprintf(stderr, "w: overwrite the uncompressed bytes from <offset> with <patch_file>, recompressing only the touched blocks\n");
+	fprintf(stderr, "t: keep only the first <keep_len> uncompressed bytes of the input (with -a: then append)\n");
+	fprintf(stderr, "a: append <tail_file> to the uncompressed bytes, compressing only the blocks from the cut on; alone it keeps everything\n");
 	fprintf(stderr, "i: input file\n");
 	fprintf(stderr, "o: output file\n");
 }
@@ -102,8 +104,22 @@ int main(int argc, char **argv)
 	unsigned long long write_off = 0;
 	const char *patch_path = NULL;
 	int raw = 0;
-	while ((opt = getopt(argc, argv, "dcRb:g:i:o:r:w:")) != -1) {
+	int use_keep = 0;
+	unsigned long long keep_len = 0;
+	const char *tail_path = NULL;
+	while ((opt = getopt(argc, argv, "dcRb:g:i:o:r:w:t:a:")) != -1) {
 		switch (opt) {
+		case 't': {                  /* keep only the first keep_len uncompressed bytes */
+			char *rest = NULL;
+			keep_len = strtoull(optarg, &rest, 10);
+			if (rest == optarg || *rest != '\0' || optarg[0] == '-' || optarg[0] == '+' || optarg[0] == ' ') {
+				fprintf(stderr, "-t wants <keep_len> in bytes, got '%s'\n", optarg);
+				return -2;
+			}
+			use_keep = 1;
+			break;
+		}
+		case 'a': tail_path = optarg; break;
 		case 'w': {                  /* overwrite the uncompressed bytes from offset with the patch file's */
 			char *colon = NULL;
 			write_off = strtoull(optarg, &colon, 10);
@@ -156,6 +172,11 @@ int main(int argc, char **argv)
 	}
 	if (raw && (use_range || use_write)) {
 		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
+		return -2;
+	}
+	const int use_resize = use_keep || tail_path;
+	if (use_resize && (compress || use_range || use_write || raw)) {
+		fprintf(stderr, "-t and -a resize a compressed file: they do not go with -c, -r, -w or -R\n");
 		return -2;
 	}
 	if (use_gpu) {
@@ -245,6 +266,35 @@ int main(int argc, char **argv)
 			gettimeofday(&t1, NULL);
 			rt.run = get_runtime(&t0, &t1);
 		}
+	} else if (use_resize) {
+		/* only the block keep_len cuts is decoded, only it and the blocks behind it are compressed; the output is the new stream */
+		struct host_buffer_context tail = { 0 };
+		tail.max = ULONG_MAX;
+		tail.file_name = tail_path;
+		if (tail_path && slurp(tail_path, &tail))
+			return -1;
+		const int tail_pinned = tail_path && g_pinned;   /* (buffer_alloc clears g_pinned when it falls back to malloc) */
+		if (!use_keep) {                 /* -a alone keeps everything */
+			uint64_t total = 0;
+			if (snappy_total_len_host(&input, &total) != SNAPPY_OK)
+				return -1;
+			keep_len = total;
+		}
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		if (use_gpu) {
+			st = snappy_resize_gpu(&input, keep_len, tail_path ? &tail : NULL, &output, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = snappy_resize_host(&input, keep_len, tail_path ? &tail : NULL, &output);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+		if (tail_pinned)
+			snappy_hip_host_free(tail.buffer);
+		else
+			free(tail.buffer);
 	} else if (use_range) {
 		/* only the blocks the range touches are decoded; the output holds exactly the range's bytes */
 		output.buffer = NULL;
@@ -285,7 +335,7 @@ int main(int argc, char **argv)
 	if (spill(out_path, &output))
 		return -1;
 
-	if (compress || use_write) {          /* (-w: the new stream against the old one) */
+	if (compress || use_write || use_resize) {          /* (-w, -t, -a: the new stream against the old one) */
 		printf("Compressed %ld bytes to: %s\n", output.length, out_path);
 		printf("Compression ratio: %f\n", 1 - (double)output.length / (double)input.length);
 	} else {

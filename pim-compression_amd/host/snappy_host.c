@@ -473,3 +473,96 @@ snappy_status snappy_update_range_host(struct host_buffer_context *input, struct
 	output->length = (unsigned long)(s.p - out);
 	return SNAPPY_OK;
 }
+
+/* The uncompressed length in the header of a whole framed file (dpu_snappy -a alone keeps that many bytes). */
+snappy_status snappy_total_len_host(const struct host_buffer_context *input, uint64_t *total_len)
+{
+	uint32_t total;
+	if (!varint_get(input->buffer, input->buffer + input->length, &total)) {
+		fprintf(stderr, "Failed to read the stream header\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	*total_len = total;
+	return SNAPPY_OK;
+}
+
+/* dpu_snappy -t / -a: the first keep_len bytes of the plaintext of a whole framed file, then tail's bytes (tail may be NULL).
+ * The chain is walked once, to its end; the blocks wholly in front of keep_len are copied, the block keep_len cuts is decoded
+ * (in full, unless keep_len lies on a block boundary) and, with every block behind it up to the new last one, compressed; the
+ * header gets the new length.  output->buffer is malloc'd here. */
+snappy_status snappy_resize_host(struct host_buffer_context *input, uint64_t keep_len, struct host_buffer_context *tail,
+                                 struct host_buffer_context *output)
+{
+	const uint8_t *const end = input->buffer + input->length;
+	const uint64_t length = tail ? tail->length : 0;
+	uint32_t total, bs;
+	const uint8_t *ip = varint_get(input->buffer, end, &total);
+	if (ip)
+		ip = varint_get(ip, end, &bs);
+	if (!ip) {
+		fprintf(stderr, "Failed to read the stream header\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (keep_len > total) {
+		fprintf(stderr, "keep length %lu lies beyond the %u uncompressed bytes\n", (unsigned long)keep_len, total);
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (length > 0xffffffffUL - keep_len) {
+		fprintf(stderr, "%lu + %lu bytes do not fit the format's 32-bit length\n", (unsigned long)keep_len, (unsigned long)length);
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (bs == 0 || bs > 65535 || (length && !tail->buffer))
+		return SNAPPY_INVALID_INPUT;
+	const uint64_t nb = ((uint64_t)total + bs - 1) / bs;
+	const uint64_t new_total = keep_len + length, new_nb = (new_total + bs - 1) / bs, kept = keep_len / bs;
+	/* the chain (:227-231): where the kept blocks end (= where the cut block starts), and that it ends with the file */
+	const uint8_t *const first = ip, *cut = ip;
+	for (uint64_t b = 0; b < nb; b++) {
+		if (end - ip < 4)
+			return SNAPPY_INVALID_INPUT;
+		const uint32_t csz = load32(ip);
+		if ((unsigned long)(end - ip - 4) < csz)
+			return SNAPPY_INVALID_INPUT;
+		ip += 4ul + csz;
+		if (b + 1 == kept)
+			cut = ip;
+	}
+	if (ip != end)
+		return SNAPPY_INVALID_INPUT;                           /* bytes behind the last block */
+	const unsigned long cap = 16 + (unsigned long)(cut - first) + (new_nb - kept) * (4ul + 32 + bs + bs / 6);
+	uint8_t *out = malloc(cap), *tmp = malloc((unsigned long)bs + 16);
+	uint16_t *tab = malloc(TABLE_MAX * sizeof(*tab));
+	snappy_status st = (out && tmp && tab) ? SNAPPY_OK : SNAPPY_BUFFER_TOO_SMALL;
+	struct sink s = { out };
+	if (st == SNAPPY_OK) {
+		s.p = varint_put(s.p, (uint32_t)new_total);          /* the header changes length with the new total */
+		s.p = varint_put(s.p, bs);
+		memcpy(s.p, first, (size_t)(cut - first));
+		s.p += cut - first;
+	}
+	for (uint64_t b = kept; b < new_nb && st == SNAPPY_OK; b++) {
+		const uint64_t begin = b * bs, n = begin + bs < new_total ? bs : new_total - begin;
+		const uint64_t head = b == kept ? keep_len - begin : 0;
+		if (head) {
+			const uint64_t blen = begin + bs < total ? bs : total - begin;
+			const uint32_t csz = load32(cut);
+			if (decompress_block_host(cut + 4, cut + 4 + csz, tmp, tmp, tmp + blen) != tmp + blen) {
+				st = SNAPPY_INVALID_INPUT;
+				break;
+			}
+		}
+		if (n > head)
+			memcpy(tmp + head, tail->buffer + (begin + head - keep_len), n - head);
+		host_compress_block(tmp, (uint32_t)n, &s, tab);
+	}
+	free(tmp);
+	free(tab);
+	if (st != SNAPPY_OK) {
+		free(out);
+		return st;
+	}
+	output->buffer = out;
+	output->curr = s.p;
+	output->length = (unsigned long)(s.p - out);
+	return SNAPPY_OK;
+}

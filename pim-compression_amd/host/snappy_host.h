@@ -23,6 +23,12 @@ snappy_status snappy_decompress_range_host(struct host_buffer_context *input, st
 /* dpu_snappy -w: patch over plaintext bytes [offset, offset + patch->length), recompressing only the blocks it touches */
 snappy_status snappy_update_range_host(struct host_buffer_context *input, struct host_buffer_context *patch, uint64_t offset,
                                        struct host_buffer_context *output);
+/* the uncompressed length in the header of a whole framed file (dpu_snappy -a alone keeps that many bytes) */
+snappy_status snappy_total_len_host(const struct host_buffer_context *input, uint64_t *total_len);
+/* dpu_snappy -t / -a: the first keep_len bytes of the plaintext, then tail's (tail may be NULL); only the block keep_len cuts is
+ * decoded, only it and the blocks behind it are compressed */
+snappy_status snappy_resize_host(struct host_buffer_context *input, uint64_t keep_len, struct host_buffer_context *tail,
+                                 struct host_buffer_context *output);
 /* dpu_snappy -R: the original ("raw") Snappy format, varint(length) + one element stream.  Compression writes the elements of
  * the input's block_size fragments without their size words (output from setup_compression); decompression (output from
  * setup_decompression, input->curr behind the header) takes streams of any compressor. */

@@ -101,6 +101,13 @@ def lib():
         L.snappy_hip_update_scratch_bytes.argtypes = [u32, u32, u32, u32]
         L.snappy_hip_update_ranges.restype = ctypes.c_int
         L.snappy_hip_update_ranges.argtypes = [vp, u32, u32, vp, u32, vp, vp, u64, vp, vp, vp, u32, vp, u64, vp]
+        L.snappy_hip_resize_scratch_bytes.restype = u64
+        L.snappy_hip_resize_scratch_bytes.argtypes = [u32, u32, u32, u32, u32]
+        L.snappy_hip_resize.restype = ctypes.c_int
+        L.snappy_hip_resize.argtypes = [vp, u32, u32, u32, u32, vp, u32, vp, vp, u64, vp, vp, vp, vp, u64, vp]
+        L.snappy_resize_gpu.restype = ctypes.c_int
+        L.snappy_resize_gpu.argtypes = [ctypes.POINTER(HostBufferContext), u64, ctypes.POINTER(HostBufferContext),
+                                        ctypes.POINTER(HostBufferContext), ctypes.POINTER(ProgramRuntime)]
         L.snappy_hip_raw_decompress_batch.restype = ctypes.c_int
         L.snappy_hip_raw_decompress_batch.argtypes = [vp, u32, vp, vp, vp]
         L.snappy_hip_raw_compress_bound.restype = u64
@@ -411,6 +418,46 @@ def update_ranges(d_desc, total_len, block_size, d_writes, write_count, d_write_
     return d_scratch
 
 
+# growing and shrinking one container (snappy_hip_resize)
+SEGMENT_DTYPE = np.dtype([("src", "<u8"), ("length", "<u8")])   # snappy_hip_segment
+
+
+def resize_scratch_bytes(block_size, old_blocks, new_total_len, keep_len, segment_count):
+    """Scratch of snappy_hip_resize on the current device (0 for a bad block size)."""
+    return int(lib().snappy_hip_resize_scratch_bytes(block_size, old_blocks, new_total_len, keep_len, segment_count))
+
+
+def make_segments(entries, device="cuda"):
+    """entries: list of (src, length) with src a device address (int) -> device tensor of snappy_hip_segment."""
+    import torch
+    arr = np.zeros(max(len(entries), 1), dtype=SEGMENT_DTYPE)
+    for i, (src, length) in enumerate(entries):
+        arr[i] = (src, length)
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
+def resize(d_desc, total_len, block_size, keep_len, new_total_len, d_segments, segment_count, d_segment_status, d_new_stream, d_new_offsets,
+           d_new_stream_len, d_result, d_scratch=None, capacity=None):
+    """Enqueue snappy_hip_resize on the current stream.  d_desc: make_stream_descs() tensor of ONE descriptor (block_offsets
+    filled in), d_segments: make_segments() tensor, d_segment_status: device int32 tensor of segment_count entries,
+    d_new_stream: device uint8 tensor (capacity: its size), d_new_offsets: device int64 tensor of num_blocks(new_total_len) + 1
+    entries, d_new_stream_len: device int64 tensor of one entry, d_result: device int32 tensor of two.  d_scratch: 256-byte
+    aligned device uint8 tensor (default: a fresh one).  Nothing is synchronised."""
+    import torch
+    if not 0 <= new_total_len <= 0xffffffff or not 0 <= keep_len <= 0xffffffff:
+        raise SnappyHipError("snappy_hip_resize: keep_len and new_total_len must fit the format's 32 bits")
+    if d_scratch is None:
+        d_scratch = torch.empty(resize_scratch_bytes(block_size, num_blocks(total_len, block_size), new_total_len, keep_len, segment_count),
+                                dtype=torch.uint8, device=d_new_stream.device)
+    _check(lib().snappy_hip_resize(d_desc.data_ptr(), total_len, block_size, keep_len, new_total_len,
+                                   d_segments.data_ptr() if segment_count else None, segment_count,
+                                   d_segment_status.data_ptr() if segment_count else None, d_new_stream.data_ptr(),
+                                   d_new_stream.numel() if capacity is None else capacity, d_new_offsets.data_ptr(),
+                                   d_new_stream_len.data_ptr(), d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(),
+                                   _stream_handle(torch)), "snappy_hip_resize")
+    return d_scratch
+
+
 # batches of raw Snappy streams, described on the device (snappy_hip_raw_decompress_batch / snappy_hip_raw_compress_batch)
 RAW_DST_TOO_SMALL = 5
 RAW_TOO_LARGE = 6
@@ -544,6 +591,29 @@ def update_range_host(stream, offset, data, out_capacity=None):
         out = HostBufferContext(b"<memory>", buf, buf, 0, out_capacity)
     rt = ProgramRuntime()
     st = lib().snappy_update_range_gpu(ctypes.byref(inp), ctypes.byref(patch), offset, ctypes.byref(out), ctypes.byref(rt))
+    new = ctypes.string_at(out.buffer, out.length) if st == SNAPPY_OK else b""
+    if out.buffer:
+        libc().free(out.buffer)
+    return st, new, rt.as_dict()
+
+
+def resize_host(stream, keep_len, tail=None, out_capacity=None):
+    """snappy_resize_gpu on a whole framed file held in host memory: the first keep_len bytes of its plaintext, then `tail`
+    (bytes, or None for a NULL tail) -> (status, new stream bytes, runtime dict).  out_capacity: as in compress_host."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
+    tail_ref = None
+    if tail is not None:
+        b = np.frombuffer(tail, dtype=np.uint8).copy() if len(tail) else np.zeros(1, dtype=np.uint8)
+        tail_ctx = HostBufferContext(b"<memory>", b.ctypes.data, b.ctypes.data, len(tail), (1 << 64) - 1)
+        tail_ref = ctypes.byref(tail_ctx)
+    if out_capacity is None:
+        out = HostBufferContext(b"<memory>", None, None, 0, (1 << 64) - 1)
+    else:
+        buf = libc().malloc(max(1, out_capacity))
+        out = HostBufferContext(b"<memory>", buf, buf, 0, out_capacity)
+    rt = ProgramRuntime()
+    st = lib().snappy_resize_gpu(ctypes.byref(inp), keep_len, tail_ref, ctypes.byref(out), ctypes.byref(rt))
     new = ctypes.string_at(out.buffer, out.length) if st == SNAPPY_OK else b""
     if out.buffer:
         libc().free(out.buffer)
