@@ -336,6 +336,7 @@ SNAPPY_HIP_API int snappy_hip_decompress_ranges(const snappy_hip_stream_desc *d_
  *   A dirty block that the writes cover completely (one write or several adjacent ones) is not decoded at all: its old bytes
  *   cannot matter.  A clean block is copied, NOT decoded: damage inside its payload with an intact link travels along
  *   into the new stream (snappy_hip_decompress_blocks of the new stream reports it, as it would for the old one).
+ *   snappy_hip_check_blocks (below) finds such damage in the old or the new stream without decoding either.
  * No write at all gives a copy of the stream (chain checked); total_len == 0 gives the header.
  *
  * d_scratch: 256-byte aligned device workspace of at least snappy_hip_update_scratch_bytes(...) bytes for the same
@@ -409,6 +410,7 @@ SNAPPY_HIP_API int snappy_hip_update_ranges(const snappy_hip_stream_desc *d_desc
  *                                   d_new_offsets are unspecified; the old stream is intact.
  *   Blocks wholly behind keep_len are never read: damage there cannot matter.  With keep_len on a block boundary nothing is
  *   decoded at all.  A kept block is copied, NOT decoded: damage inside its payload with an intact link travels along.
+ *   snappy_hip_check_blocks (below) finds such damage in the old or the new stream without decoding either.
  *   keep_len == total_len without segments gives the stream again (chain checked, a short last block decoded and compressed
  *   again); new_total_len == 0 gives the header.
  *
@@ -438,6 +440,46 @@ SNAPPY_HIP_API int snappy_hip_resize(const snappy_hip_stream_desc *d_desc, uint3
                       const snappy_hip_segment *d_segments, uint32_t segment_count, uint32_t *d_segment_status,
                       uint8_t *d_new_stream, uint64_t new_stream_capacity, uint64_t *d_new_offsets,
                       uint64_t *d_new_stream_len, uint32_t *d_result, void *d_scratch, uint64_t scratch_bytes, void *stream);
+
+/*
+ * Containers checked without being decoded: would every block be SNAPPY_HIP_BLOCK_OK in snappy_hip_decompress_blocks?  A
+ * block's verdict there depends on the stream's bytes alone -- a rejected element, output beyond the block's length, a copy
+ * with a zero offset or one reaching before the block's first byte, a block that ends short of or beyond its output or its
+ * compressed size, a size word that leaves the stream -- so the check walks the elements of every block as the decoder does
+ * and writes nothing but verdicts: no output buffer, no stores to one, no loads of back-references.  What to run before
+ * trusting a file, after a chain of snappy_hip_update_ranges / snappy_hip_resize calls (which copy clean blocks unread), or
+ * as a scrub over resident containers.
+ *
+ * d_descs: device array of `count` snappy_hip_stream_desc as snappy_hip_decompress_ranges reads them (stream, stream_len,
+ *   block_offsets of num_blocks entries, total_len, block_size, num_blocks; result is neither read nor written, so the
+ *   descriptors of a snappy_hip_index_streams call can be passed on unchanged).  Containers of different block sizes mix in
+ *   one call.
+ * d_block_status: NULL, or a device array of `count` device pointers, any of which may be NULL.  d_block_status[i][b], when
+ *   given, is exactly what snappy_hip_decompress_blocks would write to d_status[b] for that stream, those offsets and that
+ *   total_len.
+ * d_results: device, 4 u32 per container, always written:
+ *   [4i]     SNAPPY_HIP_BLOCK_OK             every block is OK (total_len == 0: no blocks, OK);
+ *            SNAPPY_HIP_BLOCK_INVALID        some block is not;
+ *            SNAPPY_HIP_RANGE_OUT_OF_BOUNDS  a malformed descriptor -- block_size 0 or above 65535, num_blocks not
+ *                                            ceil(total_len / block_size), null block_offsets with blocks present, a null
+ *                                            stream with stream_len > 0 -- or a container whose blocks lie beyond the 2^31st
+ *                                            of the call.  Nothing of it is read.
+ *   [4i + 1] the number of invalid blocks;
+ *   [4i + 2] the lowest invalid block index, 0xffffffff when there is none;
+ *   [4i + 3] 0.
+ * It checks ELEMENTS, NOT LINKS: a block is read at the offset the descriptor gives, and a block whose offset is garbage gets
+ * the decoder's verdict for that offset.  A caller whose offsets are unproven runs snappy_hip_verify_index or
+ * snappy_hip_index_streams first.
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_check_scratch_bytes(count) bytes (count + 2 u64, rounded
+ * up to 256), not shared with a launch that runs concurrently; contents need not be initialised.  The grid is K2's
+ * (SNAPPY_HIP_K2_WAVES caps it).
+ * count == 0 is OK and launches nothing.  The call only enqueues work on `stream`; it never synchronises and never calls the
+ * allocator.  SNAPPY_HIP_ERR_ARG (host side): null arrays with count > 0, a scratch that is too small or misaligned.
+ * DESIGN.md 3.8 has the measured cost beside a decode of the same stream.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_check_scratch_bytes(uint32_t count);
+SNAPPY_HIP_API int snappy_hip_check_blocks(const snappy_hip_stream_desc *d_descs, uint32_t count, uint32_t *const *d_block_status,
+                            uint32_t *d_results, void *d_scratch, uint64_t scratch_bytes, void *stream);
 
 /* ---- 1a. batches of raw Snappy streams, described on the device ---------- */
 
@@ -489,6 +531,17 @@ typedef struct snappy_hip_raw_item {
  */
 SNAPPY_HIP_API int snappy_hip_raw_decompress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint64_t *d_out_len,
                                     uint32_t *d_status, void *stream);
+
+/*
+ * Item i's src[0, src_len) checked without being decoded; dst and dst_capacity are ignored.  For every item (d_status[i],
+ * d_out_len[i]) equals what snappy_hip_raw_decompress_batch gives the same src and src_len with a sufficient dst_capacity:
+ * SNAPPY_HIP_BLOCK_OK, SNAPPY_HIP_BLOCK_INVALID or SNAPPY_HIP_RAW_TOO_LARGE, never SNAPPY_HIP_RAW_DST_TOO_SMALL; d_out_len[i]
+ * = the header's length whenever the header parses.  The payload of a long literal is skipped, not read.
+ * count == 0 is OK and launches nothing.  The call only enqueues work on `stream`; it never synchronises, never calls the
+ * allocator and needs no scratch.  SNAPPY_HIP_ERR_ARG (host side): null arrays with count > 0.
+ */
+SNAPPY_HIP_API int snappy_hip_raw_check_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint64_t *d_out_len, uint32_t *d_status,
+                               void *stream);
 
 /*
  * Item i's src[0, src_len) is plaintext; its output is varint(src_len) followed by the elements K1 produces for each
@@ -581,6 +634,37 @@ SNAPPY_HIP_API snappy_status snappy_compress_raw_gpu(struct host_buffer_context 
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_raw_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                         struct program_runtime *runtime);
+
+/* ---- 1d. drop-in level: is this file intact? ----------------------------- */
+
+/*
+ * What `gzip -t` answers, for the framed stream in input (the whole file: input->buffer at its first byte, input->length =
+ * file size).  Parses the header and walks the whole u32 size chain on the host (in parallel shares where the stream is long
+ * enough), copies the stream to the current device, runs one snappy_hip_check_blocks there and copies 16 bytes back: no
+ * output buffer anywhere.  SNAPPY_OK iff the header, the chain (which must end exactly where the file does) and every block
+ * hold; SNAPPY_INVALID_INPUT otherwise.  *report (may be NULL), always filled:
+ *   blocks            the header's block count (0 when the header cannot be read);
+ *   bad_blocks        blocks that do not decode; with a broken header or chain 1, and nothing is sent to the device;
+ *   first_bad_block   the lowest such block, or the block whose link fails (the one whose size word is not in the file, that
+ *                     ends beyond it, or -- for bytes left behind the chain -- the last one); 0 for a broken header;
+ *                     UINT64_MAX when the file is intact;
+ *   first_bad_offset  the file offset of that block's size word (0 for a broken header, UINT64_MAX when intact).
+ * No sharding.  Fills every field of *runtime.
+ */
+typedef struct snappy_hip_check_report {
+	uint64_t blocks, bad_blocks, first_bad_block, first_bad_offset;
+} snappy_hip_check_report;
+SNAPPY_HIP_API snappy_status snappy_check_gpu(struct host_buffer_context *input, snappy_hip_check_report *report,
+                               struct program_runtime *runtime);
+
+/*
+ * The same for the raw Snappy stream in input: one item through snappy_hip_raw_check_batch on the current device (one
+ * wavefront walks the whole stream).  *uncompressed_len (may be NULL) = the header's length, 0 when it cannot be read.
+ * SNAPPY_INVALID_INPUT: a malformed header, a stream or length above SNAPPY_HIP_RAW_MAX_LEN, or elements that would not decode.
+ * Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_check_raw_gpu(struct host_buffer_context *input, uint64_t *uncompressed_len,
+                                   struct program_runtime *runtime);
 
 #ifdef __cplusplus
 }

@@ -1023,6 +1023,117 @@ snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, str
     return SNAPPY_OK;
 }
 
+// Is a framed file intact (snappy_check_gpu)?  The header and the whole size chain on the host, the whole stream to the device,
+// one snappy_hip_check_blocks, 16 bytes back.  A broken header or chain is decided here: nothing is sent to the device.
+snappy_status check_gpu_body(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)
+{
+    if (!input || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    snappy_hip_check_report none{};
+    snappy_hip_check_report& rep = report ? *report : none;
+    rep = snappy_hip_check_report{0, 0, ~0ull, ~0ull};
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length;
+    const dropin_plan::Container c = dropin_plan::open_container(buf, in_total);
+    if (c.bad) {
+        rep = snappy_hip_check_report{0, 1, 0, 0};
+        (void)call.done_on_host();
+        return say(c.bad);
+    }
+    const uint64_t nb = c.nb;
+    rep.blocks = nb;
+    std::vector<uint64_t> off;
+    const unsigned walk_threads = (unsigned)std::max(1, env_int("SNAPPY_HIP_HOST_WALK_THREADS",
+                                                               (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
+    if (!host_chain::parallel_walk(buf, in_total, c.hdr, nb, c.bs, walk_threads, off)) {
+        // the serial walk, which also names the link that fails (every block needs its four size bytes: checked before
+        // anything is sized by the header's count)
+        const uint64_t fit = std::min<uint64_t>(nb, (in_total - c.hdr) / 4);
+        off.assign(fit + 1, 0);
+        const dropin_plan::Walk w = dropin_plan::walk_chain(buf, in_total, 0, off.data(), {0, c.hdr}, fit);
+        const bool stopped = w.stop != dropin_plan::kDone || fit < nb;
+        if (stopped || w.at != in_total) {
+            rep.bad_blocks = 1;
+            rep.first_bad_block = stopped ? w.block : (nb ? nb - 1 : 0);
+            rep.first_bad_offset = !stopped ? (nb ? off[nb - 1] : c.hdr) : (w.stop == dropin_plan::kLeaves ? off[w.block] : w.at);
+            (void)call.done_on_host();
+            if (stopped) return say(dropin_plan::refuse("truncated stream (block %lu of %lu)", (unsigned long)rep.first_bad_block, (unsigned long)nb));
+            return say(dropin_plan::refuse("%lu bytes behind the last block", (unsigned long)(in_total - w.at)));
+        }
+    }
+    if (nb == 0) return call.done_on_host();
+    if (snappy_status st = call.need_device()) return st;
+    const uint64_t scratch_bytes = snappy_hip_check_scratch_bytes(1);
+
+    uint8_t *d_stream = nullptr, *d_scratch = nullptr;
+    uint64_t* d_boff = nullptr;
+    snappy_hip_stream_desc* d_desc = nullptr;
+    uint32_t* d_result = nullptr;
+    if (snappy_status st = call.buffers({{&d_stream, in_total}, {&d_boff, nb * sizeof(uint64_t)}, {&d_desc, sizeof *d_desc},
+                                         {&d_result, 4 * sizeof(uint32_t)}, {&d_scratch, scratch_bytes}}))
+        return st;
+    const snappy_hip_stream_desc desc{d_stream, in_total, d_boff, nullptr, c.total, c.bs, c.hdr, (uint32_t)nb};
+    if (snappy_status st = call.upload({{d_stream, buf, in_total}, {d_boff, off.data(), nb * sizeof(uint64_t)}, {d_desc, &desc, sizeof desc}}))
+        return st;
+    if (snappy_status st = call.launch("check", [&] { return snappy_hip_check_blocks(d_desc, 1, nullptr, d_result, d_scratch, scratch_bytes, nullptr); }))
+        return st;
+    uint32_t words[4] = {0xffffffffu, 0, 0, 0};
+    if (snappy_status st = call.copy_out([&] { return call.download({{words, d_result, sizeof words}}); })) return st;
+    if (snappy_status st = call.free_buffers()) return st;
+    if (words[0] == SNAPPY_HIP_BLOCK_OK) return SNAPPY_OK;
+    if (words[0] == SNAPPY_HIP_BLOCK_INVALID && words[2] < nb) {
+        rep.bad_blocks = words[1];
+        rep.first_bad_block = words[2];
+        rep.first_bad_offset = off[words[2]];
+        fprintf(stderr, "snappy_hip: %u of %lu blocks do not decode, the first is block %u at offset %lu\n", words[1], (unsigned long)nb, words[2],
+                (unsigned long)off[words[2]]);
+    } else {
+        rep.bad_blocks = nb;
+        rep.first_bad_block = 0;
+        rep.first_bad_offset = off[0];
+        fprintf(stderr, "snappy_hip: the check did not run (result %u)\n", words[0]);
+    }
+    return SNAPPY_INVALID_INPUT;
+}
+
+// Is a raw Snappy file intact (snappy_check_raw_gpu)?  One item through snappy_hip_raw_check_batch.
+snappy_status check_raw_gpu_body(struct host_buffer_context* input, uint64_t* uncompressed_len, struct program_runtime* runtime)
+{
+    if (!input || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    if (uncompressed_len) *uncompressed_len = 0;
+    const uint64_t in_len = input->length;
+    uint32_t length = 0;
+    if (!get_varint32(input->buffer, in_len, &length)) {
+        (void)call.done_on_host();
+        return say(dropin_plan::unreadable_header());                // (the device reads it again, by Google's rule)
+    }
+    if (in_len > SNAPPY_HIP_RAW_MAX_LEN || length > SNAPPY_HIP_RAW_MAX_LEN) {
+        (void)call.done_on_host();
+        fprintf(stderr, "snappy_hip: raw streams of more than %llu bytes are not checked\n", (unsigned long long)SNAPPY_HIP_RAW_MAX_LEN);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (snappy_status st = call.need_device()) return st;
+    uint8_t* d_in = nullptr;
+    snappy_hip_raw_item* d_item = nullptr;
+    RawVerdict* d_verdict = nullptr;
+    if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict}})) return st;
+    const snappy_hip_raw_item item{d_in, in_len, nullptr, 0};
+    if (snappy_status st = call.upload({{d_in, input->buffer, in_len}, {d_item, &item, sizeof item}})) return st;
+    if (snappy_status st = call.launch("raw check", [&] { return snappy_hip_raw_check_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr); }))
+        return st;
+    RawVerdict v{};
+    v.status = 0xffffffffu;
+    if (snappy_status st = call.copy_out([&] { return call.download({{&v, d_verdict, sizeof v}}); })) return st;
+    if (snappy_status st = call.free_buffers()) return st;
+    if (v.status != SNAPPY_HIP_BLOCK_OK) {
+        fprintf(stderr, "snappy_hip: the raw stream does not decode (status %u)\n", v.status);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (uncompressed_len) *uncompressed_len = v.out_len;
+    return SNAPPY_OK;
+}
+
 // The exported pair: one call at a time per process (the cached pipeline streams and their page-locked scratch are per
 // process; the reference's entry points are single-threaded and synchronous anyway, snappy_compress.c:618), the caller's
 // current HIP device restored on every return path, and no C++ exception crosses the C boundary.
@@ -1087,6 +1198,16 @@ snappy_status snappy_compress_raw_gpu(struct host_buffer_context* input, struct 
 snappy_status snappy_decompress_raw_gpu(struct host_buffer_context* input, struct host_buffer_context* output, struct program_runtime* runtime)
 {
     return entry_guard([&] { return raw_gpu_body(false, input, output, 0, runtime); });
+}
+
+snappy_status snappy_check_gpu(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return check_gpu_body(input, report, runtime); });
+}
+
+snappy_status snappy_check_raw_gpu(struct host_buffer_context* input, uint64_t* uncompressed_len, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return check_raw_gpu_body(input, uncompressed_len, runtime); });
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include "snappy_update.hpp"
 #include "snappy_raw.hpp"
 #include "snappy_resize.hpp"
+#include "snappy_check.hpp"
 
 namespace {
 
@@ -1102,6 +1103,42 @@ int snappy_hip_raw_compress_batch(const snappy_hip_raw_item* d_items, uint32_t c
                        place, scratch + l.slots, stride, d_status);
     HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
+}
+
+// ---- checking without decoding (snappy_check.hpp) ----
+uint64_t snappy_hip_check_scratch_bytes(uint32_t count) { return snappy_hip::check_prefix_bytes(count); }
+
+int snappy_hip_check_blocks(const snappy_hip_stream_desc* d_descs, uint32_t count, uint32_t* const* d_block_status, uint32_t* d_results,
+                            void* d_scratch, uint64_t scratch_bytes, void* stream)
+{
+    static_assert(sizeof(snappy_hip_stream_desc) == sizeof(snappy_hip::StreamDesc), "snappy_hip_stream_desc layout");
+    if (count == 0) return SNAPPY_HIP_OK;
+    if (!d_descs || !d_results) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    if (scratch_bytes < snappy_hip::check_prefix_bytes(count)) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_check_scratch_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t* prefix = static_cast<uint64_t*>(d_scratch);
+    const auto* descs = reinterpret_cast<const snappy_hip::StreamDesc*>(d_descs);
+    hipLaunchKernelGGL(snappy_hip::check_plan_kernel, dim3(1), dim3(1024), 0, st, descs, count, d_results, prefix);
+    HIP_TRY(hipGetLastError());
+    return launch_counted(st, [&](uint32_t* counter) {
+        // the blocks are counted on the device, so the grid is K2's for an unbounded count
+        hipLaunchKernelGGL(snappy_hip::check_kernel, dim3(range_grid_cap()), dim3(64), 0, st, descs, count, d_block_status, d_results, prefix, counter);
+        return 0;
+    });
+}
+
+int snappy_hip_raw_check_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint64_t* d_out_len, uint32_t* d_status, void* stream)
+{
+    if (count == 0) return SNAPPY_HIP_OK;
+    if (!d_items || !d_out_len || !d_status) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    hipStream_t st = (hipStream_t)stream;
+    return launch_counted(st, [&](uint32_t* counter) {
+        const uint32_t grid = std::min(range_grid_cap(), count);
+        hipLaunchKernelGGL(snappy_hip::raw_check_kernel, dim3(grid), dim3(64), 0, st, reinterpret_cast<const snappy_hip::RawItem*>(d_items), count,
+                           d_out_len, d_status, counter);
+        return 0;
+    });
 }
 
 #ifdef SNAPPY_PAIR_PROBE

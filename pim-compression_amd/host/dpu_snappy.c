@@ -6,6 +6,7 @@
  * as in the reference.  -d never falls back to the CPU.
  *
  *   dpu_snappy [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] [-R] -T -i <input_file>
  */
 #include <getopt.h>
 #include <limits.h>
@@ -23,6 +24,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
 	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "       %s [-d] [-R] -T -i <input_file>\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
@@ -32,6 +34,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "w: overwrite the uncompressed bytes from <offset> with <patch_file>, recompressing only the touched blocks\n");
 	fprintf(stderr, "t: keep only the first <keep_len> uncompressed bytes of the input (with -a: then append)\n");
 	fprintf(stderr, "a: append <tail_file> to the uncompressed bytes, compressing only the blocks from the cut on; alone it keeps everything\n");
+	fprintf(stderr, "T: test the compressed input: would every block (with -R: the raw stream) decode?  Writes no output; exit status 1 if not\n");
 	fprintf(stderr, "i: input file\n");
 	fprintf(stderr, "o: output file\n");
 }
@@ -107,8 +110,10 @@ int main(int argc, char **argv)
 	int use_keep = 0;
 	unsigned long long keep_len = 0;
 	const char *tail_path = NULL;
-	while ((opt = getopt(argc, argv, "dcRb:g:i:o:r:w:t:a:")) != -1) {
+	int use_check = 0;
+	while ((opt = getopt(argc, argv, "dcRTb:g:i:o:r:w:t:a:")) != -1) {
 		switch (opt) {
+		case 'T': use_check = 1; break;
 		case 't': {                  /* keep only the first keep_len uncompressed bytes */
 			char *rest = NULL;
 			keep_len = strtoull(optarg, &rest, 10);
@@ -179,6 +184,10 @@ int main(int argc, char **argv)
 		fprintf(stderr, "-t and -a resize a compressed file: they do not go with -c, -r, -w or -R\n");
 		return -2;
 	}
+	if (use_check && (compress || use_range || use_write || use_resize || out_path)) {
+		fprintf(stderr, "-T tests a compressed file and writes nothing: it does not go with -c, -r, -w, -t, -a or -o\n");
+		return -2;
+	}
 	if (use_gpu) {
 		/* the overlapped copy-in / kernel / copy-out pipeline of the library keeps six HIP streams busy; HIP maps
 		 * streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The host program owns its environment, so it
@@ -193,7 +202,8 @@ int main(int argc, char **argv)
 	if (!out_path)
 		out_path = "output.txt";                             /* dpu_snappy.c:155-157 */
 	output.file_name = out_path;
-	printf("Using output file %s\n", out_path);
+	if (!use_check)
+		printf("Using output file %s\n", out_path);
 
 	g_pinned = use_gpu;
 	if (slurp(in_path, &input))
@@ -203,6 +213,40 @@ int main(int argc, char **argv)
 	memset(&rt, 0, sizeof(rt));                              /* the reference leaves this uninitialised */
 	snappy_status st;
 	struct timeval t0, t1;
+	if (use_check) {
+		/* nothing is decoded to anywhere: the verdict, one line, the exit status */
+		snappy_hip_check_report rep = { 0, 0, 0, 0 };
+		uint64_t raw_len = 0;
+		if (use_gpu) {
+			st = raw ? snappy_check_raw_gpu(&input, &raw_len, &rt) : snappy_check_gpu(&input, &rep, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = raw ? snappy_check_raw_host(&input, &raw_len) : snappy_check_host(&input, &rep);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+		if (st == SNAPPY_BUFFER_TOO_SMALL) {
+			fprintf(stderr, "Encountered Snappy error %u\n", st);
+			return -1;
+		}
+		if (raw && st == SNAPPY_OK)
+			printf("Check: OK, %lu bytes\n", (unsigned long)raw_len);
+		else if (raw)
+			printf("Check: INVALID\n");
+		else if (st == SNAPPY_OK)
+			printf("Check: OK, %lu blocks\n", (unsigned long)rep.blocks);
+		else
+			printf("Check: INVALID, %lu of %lu blocks, first bad block %lu at offset %lu\n", (unsigned long)rep.bad_blocks,
+			       (unsigned long)rep.blocks, (unsigned long)rep.first_bad_block, (unsigned long)rep.first_bad_offset);
+		printf("Pre-processing time: %f\n", rt.pre);
+		printf("Alloc time: %f\n", rt.d_alloc);
+		printf("Load time: %f\n", rt.load);
+		printf("Copy in time: %f\n", rt.copy_in);
+		printf("Host time: %f\n", rt.run);
+		printf("Copy out time: %f\n", rt.copy_out);
+		printf("Free time: %f\n", rt.d_free);
+		return st == SNAPPY_OK ? 0 : 1;
+	}
 	if (raw) {
 		/* one raw Snappy stream, either way; in -d mode one item through the batch calls of the library, which allocates
 		 * the output */

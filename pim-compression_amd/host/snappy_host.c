@@ -343,6 +343,94 @@ snappy_status snappy_decompress_raw_host(struct host_buffer_context *input, stru
 	return (op == out_end) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
 }
 
+/* ---- the check (dpu_snappy -T) ---------------------------------------------- */
+
+snappy_status snappy_check_host(const struct host_buffer_context *input, snappy_hip_check_report *report)
+{
+	const uint8_t *const end = input->buffer + input->length;
+	uint32_t total, bs;
+	report->blocks = 0;
+	report->bad_blocks = 1;
+	report->first_bad_block = 0;
+	report->first_bad_offset = 0;
+	const uint8_t *ip = varint_get(input->buffer, end, &total);
+	if (ip)
+		ip = varint_get(ip, end, &bs);
+	if (!ip) {
+		fprintf(stderr, "Failed to read the stream header\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (total && (bs == 0 || bs > 65535)) {
+		fprintf(stderr, "block size %u in the stream is outside 1..65535\n", bs);
+		return SNAPPY_INVALID_INPUT;
+	}
+	const uint64_t nb = total ? ((uint64_t)total + bs - 1) / bs : 0;
+	report->blocks = nb;
+	uint8_t *scratch = malloc(total ? bs : 1);
+	if (!scratch)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	uint64_t bad = 0, first = UINT64_MAX, first_at = UINT64_MAX, last_at = 0, b;
+	int chain = 1;
+	for (b = 0; b < nb; b++) {                           /* the chain (:227-231), every block on its own */
+		const uint64_t at = (uint64_t)(ip - input->buffer);
+		uint32_t csz = 0;
+		if (end - ip >= 4)
+			csz = load32(ip);
+		if (end - ip < 4 || (unsigned long)(end - ip - 4) < csz) {
+			chain = 0;
+			first = b;
+			first_at = at;
+			break;
+		}
+		ip += 4;
+		last_at = at;
+		const uint64_t blen = (b + 1) * (uint64_t)bs < total ? bs : total - b * (uint64_t)bs;
+		if (decompress_block_host(ip, ip + csz, scratch, scratch, scratch + blen) != scratch + blen) {
+			if (!bad) {
+				first = b;
+				first_at = at;
+			}
+			bad++;
+		}
+		ip += csz;
+	}
+	free(scratch);
+	if (chain && ip != end) {                            /* bytes behind the last block: its link does not reach the end */
+		chain = 0;
+		first = nb ? nb - 1 : 0;
+		first_at = nb ? last_at : (uint64_t)(ip - input->buffer);
+	}
+	if (!chain) {
+		fprintf(stderr, "the size chain breaks at block %lu of %lu\n", (unsigned long)first, (unsigned long)nb);
+		report->bad_blocks = 1;
+	} else {
+		report->bad_blocks = bad;
+	}
+	report->first_bad_block = first;
+	report->first_bad_offset = first_at;
+	return (chain && !bad) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
+}
+
+snappy_status snappy_check_raw_host(const struct host_buffer_context *input, uint64_t *uncompressed_len)
+{
+	const uint8_t *const end = input->buffer + input->length;
+	uint32_t total;
+	*uncompressed_len = 0;
+	const uint8_t *ip = varint_get(input->buffer, end, &total);
+	if (!ip || (ip - input->buffer == 5 && ip[-1] >= 16)) {
+		fprintf(stderr, "Failed to read decompressed length\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	*uncompressed_len = total;
+	uint8_t *scratch = malloc(total ? total : 1);
+	if (!scratch)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	const uint8_t *op = decompress_block_host(ip, end, scratch, scratch, scratch + total);
+	const int ok = op == scratch + total;
+	free(scratch);
+	return ok ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
+}
+
 /* Bytes [offset, offset + length) of a whole framed file (input->buffer at its first byte): the size chain walked up to the
  * last block the range touches, only the touched blocks decoded.  output->buffer is malloc'd here (length bytes). */
 snappy_status snappy_decompress_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,

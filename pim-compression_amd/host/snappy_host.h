@@ -34,6 +34,11 @@ snappy_status snappy_resize_host(struct host_buffer_context *input, uint64_t kee
  * setup_decompression, input->curr behind the header) takes streams of any compressor. */
 snappy_status snappy_compress_raw_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t block_size);
 snappy_status snappy_decompress_raw_host(struct host_buffer_context *input, struct host_buffer_context *output);
+/* dpu_snappy -T: is the whole framed file intact?  The chain is walked and every block decoded on its own into ONE scratch block;
+ * the verdict is decompress_block_host's.  *report as snappy_check_gpu fills it. */
+snappy_status snappy_check_host(const struct host_buffer_context *input, snappy_hip_check_report *report);
+/* dpu_snappy -T -R: the same for one raw Snappy stream (decoded into a scratch buffer of the header's length) */
+snappy_status snappy_check_raw_host(const struct host_buffer_context *input, uint64_t *uncompressed_len);
 double get_runtime(struct timeval *start, struct timeval *end);
 
 #ifdef __cplusplus

@@ -47,6 +47,14 @@ _LIB = None
 _LIBC = None
 
 
+class CheckReport(ctypes.Structure):            # snappy_hip_check_report
+    _fields_ = [("blocks", ctypes.c_uint64), ("bad_blocks", ctypes.c_uint64), ("first_bad_block", ctypes.c_uint64),
+                ("first_bad_offset", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class SnappyHipError(RuntimeError):
     pass
 
@@ -116,6 +124,16 @@ def lib():
         L.snappy_hip_raw_compress_scratch_bytes.argtypes = [u32, u32, u32]
         L.snappy_hip_raw_compress_batch.restype = ctypes.c_int
         L.snappy_hip_raw_compress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_check_scratch_bytes.restype = u64
+        L.snappy_hip_check_scratch_bytes.argtypes = [u32]
+        L.snappy_hip_check_blocks.restype = ctypes.c_int
+        L.snappy_hip_check_blocks.argtypes = [vp, u32, vp, vp, vp, u64, vp]
+        L.snappy_hip_raw_check_batch.restype = ctypes.c_int
+        L.snappy_hip_raw_check_batch.argtypes = [vp, u32, vp, vp, vp]
+        L.snappy_check_gpu.restype = ctypes.c_int
+        L.snappy_check_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(CheckReport), ctypes.POINTER(ProgramRuntime)]
+        L.snappy_check_raw_gpu.restype = ctypes.c_int
+        L.snappy_check_raw_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(u64), ctypes.POINTER(ProgramRuntime)]
         L.snappy_update_range_gpu.restype = ctypes.c_int
         L.snappy_update_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64,
                                               ctypes.POINTER(HostBufferContext), ctypes.POINTER(ProgramRuntime)]
@@ -507,6 +525,67 @@ def raw_compress_batch(d_items, count, block_size, max_fragments, d_out_len, d_s
     return d_scratch
 
 
+# checking without decoding (snappy_hip_check_blocks, snappy_hip_raw_check_batch)
+CHECK_NONE = 0xffffffff
+
+
+def check_scratch_bytes(count):
+    """Scratch of snappy_hip_check_blocks for `count` containers."""
+    return int(lib().snappy_hip_check_scratch_bytes(count))
+
+
+def check_blocks(d_descs, count, d_results, d_block_status=None, d_scratch=None):
+    """Enqueue snappy_hip_check_blocks on the current stream.  d_descs: make_stream_descs() tensor (block_offsets filled in; result
+    is not touched), d_results: device int32 tensor of 4 * count entries, d_block_status: None, or a device int64 tensor of `count`
+    device addresses (0 = no status array for that container).  d_scratch: 256-byte aligned device uint8 tensor (default: a fresh
+    one).  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(check_scratch_bytes(count), 256), dtype=torch.uint8, device=d_results.device)
+    _check(lib().snappy_hip_check_blocks(d_descs.data_ptr(), count, d_block_status.data_ptr() if d_block_status is not None else None,
+                                         d_results.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(), _stream_handle(torch)),
+           "snappy_hip_check_blocks")
+    return d_scratch
+
+
+def raw_check_batch(d_items, count, d_out_len, d_status):
+    """Enqueue snappy_hip_raw_check_batch on the current stream: as raw_decompress_batch, the items' dst and dst_capacity
+    ignored.  Nothing is synchronised."""
+    import torch
+    _check(lib().snappy_hip_raw_check_batch(d_items.data_ptr(), count, d_out_len.data_ptr(), d_status.data_ptr(), _stream_handle(torch)),
+           "snappy_hip_raw_check_batch")
+
+
+def check_resident(d_stream, stream_len=None):
+    """Is the framed stream held in a CUDA uint8 tensor intact?  Indexes it (the size chain), then checks every block without
+    decoding it -> (ok, bad_blocks, first_bad_block).  A broken header or chain: (False, 1, the number of blocks the walk
+    found); first_bad_block is None when the stream is intact."""
+    import torch
+    stream_len = d_stream.numel() if stream_len is None else stream_len
+    head = bytes(d_stream[:min(10, stream_len)].cpu().numpy())
+    total, bs, hdr = parse_header(head)
+    if hdr == 0 or (total and not 1 <= bs <= 65535):
+        return False, 1, 0
+    nb = num_blocks(total, bs) if total else 0
+    if nb == 0:
+        return (True, 0, None) if stream_len == hdr else (False, 1, 0)
+    dev = d_stream.device
+    d_boff = torch.empty(nb, dtype=torch.int64, device=dev)
+    d_res = torch.full((2,), 7, dtype=torch.int32, device=dev)
+    descs = make_stream_descs([dict(stream=d_stream, stream_len=stream_len, block_offsets=d_boff, result=d_res,
+                                    total_len=total, block_size=bs, header_len=hdr, num_blocks=nb)], dev)
+    index_streams(descs, 1)
+    res = d_res.cpu().numpy()
+    if res[0] != 0 or res[1] != nb:
+        return False, 1, int(res[1]) & 0x7fffffff
+    d_results = torch.full((4,), 7, dtype=torch.int32, device=dev)
+    check_blocks(descs, 1, d_results)
+    r = [int(x) & 0xffffffff for x in d_results.cpu().numpy()]
+    if r[0] == 0:
+        return True, 0, None
+    return False, r[1], (r[2] if r[2] != CHECK_NONE else 0)
+
+
 # ---------------------------------------------------------------------------
 # drop-in pair (host buffers), driven the way dpu_snappy.c's main() drives the *_dpu functions
 # ---------------------------------------------------------------------------
@@ -644,3 +723,21 @@ def raw_compress_host(data, block_size=32768, out_capacity=None):
 def raw_decompress_host(stream, out_capacity=None):
     """snappy_decompress_raw_gpu on a whole raw Snappy stream held in host memory -> (status, plaintext, runtime dict)."""
     return _raw_host(lambda i, o, r: lib().snappy_decompress_raw_gpu(i, o, r), stream, out_capacity)
+
+
+def check_host(stream):
+    """snappy_check_gpu on a whole framed file held in host memory -> (status, report dict, runtime dict)."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
+    rep, rt = CheckReport(), ProgramRuntime()
+    st = lib().snappy_check_gpu(ctypes.byref(inp), ctypes.byref(rep), ctypes.byref(rt))
+    return st, rep.as_dict(), rt.as_dict()
+
+
+def check_raw_host(stream):
+    """snappy_check_raw_gpu on a whole raw Snappy stream held in host memory -> (status, uncompressed length, runtime dict)."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
+    length, rt = ctypes.c_uint64(0), ProgramRuntime()
+    st = lib().snappy_check_raw_gpu(ctypes.byref(inp), ctypes.byref(length), ctypes.byref(rt))
+    return st, int(length.value), rt.as_dict()
