@@ -489,11 +489,13 @@ SNAPPY_HIP_API int snappy_hip_check_blocks(const snappy_hip_stream_desc *d_descs
  * hold, and what every other Snappy library reads.  Many independent buffers, each described by one 32-byte item that the
  * kernels read from DEVICE memory (the host never sees the items), for both directions.
  *
- * ONE RAW STREAM IS ONE WAVEFRONT'S WORK: element boundaries in a raw stream cannot be found without parsing it, so a stream
- * cannot be split among wavefronts the way the framed format's blocks are.  From this project's figure of 0.5-0.6 ms per
- * 32 KiB block and wavefront that is an estimated 55-65 MB/s per stream (an estimate, not a measurement of this kernel); the
- * device is full only with thousands of items.  Decoding ONE large raw file on the GPU is therefore slower than the host
- * mode.  That is a property of the format.  (Compression has no such limit: the fragments of one item compress in parallel.)
+ * ONE RAW STREAM IS ONE WAVEFRONT'S WORK in snappy_hip_raw_decompress_batch: element boundaries in a raw stream cannot be
+ * found without parsing it, so that call does not split a stream among wavefronts the way the framed format's blocks are.
+ * From this project's figure of 0.5-0.6 ms per 32 KiB block and wavefront that is an estimated 55-65 MB/s per stream (an
+ * estimate, not a measurement of this kernel); the device is full only with thousands of items.  Decoding ONE large raw file
+ * with that call is therefore slower than the host mode.  That is a property of that call, not of the format: streams are
+ * built from independently compressed fragments, and snappy_hip_raw_decompress_split_batch (below) finds and proves them.
+ * (Compression has no such limit: the fragments of one item compress in parallel.)
  */
 typedef struct snappy_hip_raw_item {
 	const void *src;        /* device: the input of this item, any alignment            */
@@ -542,6 +544,43 @@ SNAPPY_HIP_API int snappy_hip_raw_decompress_batch(const snappy_hip_raw_item *d_
  */
 SNAPPY_HIP_API int snappy_hip_raw_check_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint64_t *d_out_len, uint32_t *d_status,
                                void *stream);
+
+/*
+ * snappy_hip_raw_decompress_batch with every LARGE item decoded by many wavefronts.  For every item (d_status[i],
+ * d_out_len[i]) equals what snappy_hip_raw_decompress_batch gives the same item; when the status is SNAPPY_HIP_BLOCK_OK,
+ * dst[0, length) does too; whatever the streams hold, nothing outside [dst, dst + length) is written.
+ * How: streams are built from fragments -- Google's compressor, pyarrow and snappy_hip_raw_compress_batch compress fixed-size
+ * pieces of the plaintext independently -- so at every multiple of the fragment size an element starts and no copy reaches
+ * back across it.  The call cuts the compressed bytes into segments, walks the element chains of every segment in parallel,
+ * joins them along the item (the one serial step: a table lookup per segment), finds the element that starts each UNIT of
+ * unit_len output bytes, and decodes every unit with the strict decoder as a stream of its own, which refuses a copy that
+ * reaches before the unit.  That last step is the proof: an item whose units all decode is byte for byte the serial decode.
+ * Every other item -- not built that way, damaged, or beyond the limits below -- FALLS BACK to the serial decoder inside the
+ * same call, so the result never depends on the shape of the stream, only the time does (csrc/snappy_raw_split.hpp).
+ *   unit_len       output bytes per independent piece; 0 = 65,536 (what Google's compressor and pyarrow use).  At least 256.
+ *                  For the output of snappy_hip_raw_compress_batch: its block_size or a multiple of it.
+ *   segment_bytes  compressed bytes per segment; 0 = the default, 16 KiB (the fastest of 16 / 64 / 256 KiB measured, DESIGN.md
+ *                  3.9).  A multiple of 64, at least 128.
+ *   max_segments,  what the scratch has room for: the segments (ceil((src_len - header) / segment_bytes)) and the units
+ *   max_units      (ceil(length / unit_len)) of the large items are counted in item order; an item whose segments or units
+ *                  lie beyond either limit, and every large item behind it, is decoded serially.  That is not an error.
+ * An item is LARGE when its header's length exceeds unit_len and it has more than one segment.
+ * d_result, 4 words, always written: [0] items decoded by the split path, [1] items sent straight to the serial decoder
+ * because they are not large, [2] large items that fell back to the serial decoder, [3] 0.  Items settled by their header
+ * (a bad header, TOO_LARGE, DST_TOO_SMALL, a length of 0) are in none of them.
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_raw_decompress_split_scratch_bytes(...) bytes (0 for bad
+ * parameters), not shared with a launch that runs concurrently; contents need not be initialised.  It holds two u64 and a u32
+ * per item, 528 bytes per segment and a u32 per unit.
+ * The call only enqueues work on `stream` (six kernels); it never synchronises and never calls the allocator; the verdicts
+ * stay on the device.  SNAPPY_HIP_ERR_ARG (host side): a bad unit_len or segment_bytes, a null d_result, null arrays with
+ * count > 0, a scratch that is misaligned or too small.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_raw_decompress_split_scratch_bytes(uint32_t count, uint32_t unit_len, uint32_t segment_bytes,
+                                                       uint64_t max_segments, uint64_t max_units);
+SNAPPY_HIP_API int snappy_hip_raw_decompress_split_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t unit_len,
+                                          uint32_t segment_bytes, uint64_t max_segments, uint64_t max_units,
+                                          uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result, void *d_scratch,
+                                          uint64_t scratch_bytes, void *stream);
 
 /*
  * Item i's src[0, src_len) is plaintext; its output is varint(src_len) followed by the elements K1 produces for each
@@ -634,6 +673,16 @@ SNAPPY_HIP_API snappy_status snappy_compress_raw_gpu(struct host_buffer_context 
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_raw_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                         struct program_runtime *runtime);
+
+/*
+ * snappy_decompress_raw_gpu through snappy_hip_raw_decompress_split_batch (1a): the same file, the same output, the same
+ * verdicts, but a large stream is decoded by many wavefronts where it is built from independent pieces of unit_len output
+ * bytes (0 = 65,536, what Google's compressor and pyarrow write; for a file of `dpu_snappy -c -R -b N`: N or a multiple),
+ * and by the serial decoder inside the same call where it is not.  One item, limits sized from the file, the default
+ * segment size.  SNAPPY_INVALID_INPUT also for a unit_len between 1 and 255.  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_raw_split_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                              uint32_t unit_len, struct program_runtime *runtime);
 
 /* ---- 1d. drop-in level: is this file intact? ----------------------------- */
 

@@ -955,19 +955,20 @@ snappy_status resize_gpu_body(struct host_buffer_context* input, uint64_t keep_l
 struct RawVerdict {            // what one item's call leaves on the device
     uint64_t out_len;
     uint32_t status;
-    uint32_t result[2];
+    uint32_t result[4];        // (compress: two words; the split decode: four)
     uint32_t pad;
 };
 
-// compress = true: plaintext -> raw stream at `block_size` fragments; false: raw stream -> plaintext
+// compress = true: plaintext -> raw stream at `block_size` fragments; false: raw stream -> plaintext, by one wavefront, or --
+// split_unit >= 0 -- by snappy_hip_raw_decompress_split_batch at that unit_len (0 = its default), limits sized from the file
 snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
-                           struct program_runtime* runtime)
+                           struct program_runtime* runtime, int64_t split_unit = -1)
 {
     if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
     PhasedCall call(runtime);
     const uint64_t in_len = input->length;
-    uint64_t capacity = 0, scratch_bytes = 0;
-    uint32_t fragments = 0;
+    uint64_t capacity = 0, scratch_bytes = 0, segments = 0, units = 0;
+    uint32_t fragments = 0, unit_len = 0;
     if (compress) {
         if (!block_size_ok(block_size)) return say(dropin_plan::bad_block_size(block_size, ""));
         if (in_len >> 32) {
@@ -985,6 +986,16 @@ snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, str
             return SNAPPY_INVALID_INPUT;
         }
         capacity = length;
+        if (split_unit >= 0) {
+            if (split_unit > 0xffffffffll || (split_unit && split_unit < 256)) {
+                fprintf(stderr, "snappy_hip: the unit length of a split decode is 0 (the default) or at least 256\n");
+                return SNAPPY_INVALID_INPUT;
+            }
+            unit_len = split_unit ? (uint32_t)split_unit : 65536u;
+            segments = in_len / 16384u + 1;                                     // (the default segment_bytes)
+            units = (uint64_t)length / unit_len + 1;
+            scratch_bytes = snappy_hip_raw_decompress_split_scratch_bytes(1, unit_len, 0, segments, units);
+        }
         if (snappy_status st = claim_output(output, capacity)) return st;      // decode knows its size now, compress after the launch
     }
     place(output, 0);
@@ -1001,7 +1012,10 @@ snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, str
     if (snappy_status st = call.launch("raw batch", [&] {
             return compress ? snappy_hip_raw_compress_batch(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
                                                             d_verdict->result, d_scratch, scratch_bytes, nullptr)
-                            : snappy_hip_raw_decompress_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr);
+                   : split_unit >= 0
+                       ? snappy_hip_raw_decompress_split_batch(d_item, 1, unit_len, 0, segments, units, &d_verdict->out_len, &d_verdict->status,
+                                                               d_verdict->result, d_scratch, scratch_bytes, nullptr)
+                       : snappy_hip_raw_decompress_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr);
         }))
         return st;
     RawVerdict v{};
@@ -1198,6 +1212,12 @@ snappy_status snappy_compress_raw_gpu(struct host_buffer_context* input, struct 
 snappy_status snappy_decompress_raw_gpu(struct host_buffer_context* input, struct host_buffer_context* output, struct program_runtime* runtime)
 {
     return entry_guard([&] { return raw_gpu_body(false, input, output, 0, runtime); });
+}
+
+snappy_status snappy_decompress_raw_split_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t unit_len,
+                                              struct program_runtime* runtime)
+{
+    return entry_guard([&] { return raw_gpu_body(false, input, output, 0, runtime, (int64_t)unit_len); });
 }
 
 snappy_status snappy_check_gpu(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)

@@ -29,6 +29,7 @@
 #include "snappy_ranges.hpp"
 #include "snappy_update.hpp"
 #include "snappy_raw.hpp"
+#include "snappy_raw_split.hpp"
 #include "snappy_resize.hpp"
 #include "snappy_check.hpp"
 
@@ -1103,6 +1104,80 @@ int snappy_hip_raw_compress_batch(const snappy_hip_raw_item* d_items, uint32_t c
                        place, scratch + l.slots, stride, d_status);
     HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
+}
+
+// ---- one large raw stream over many wavefronts (snappy_raw_split.hpp) ----
+static bool split_params(uint32_t& unit_len, uint32_t& segment_bytes)
+{
+    if (unit_len == 0) unit_len = snappy_hip::kSplitDefaultUnit;
+    if (segment_bytes == 0) segment_bytes = snappy_hip::kSplitDefaultSegment;
+    return unit_len >= 256u && segment_bytes >= 128u && segment_bytes % 64u == 0;
+}
+
+uint64_t snappy_hip_raw_decompress_split_scratch_bytes(uint32_t count, uint32_t unit_len, uint32_t segment_bytes, uint64_t max_segments,
+                                                       uint64_t max_units)
+{
+    if (!split_params(unit_len, segment_bytes)) return 0;
+    return snappy_hip::split_layout(count, max_segments, max_units).total;
+}
+
+int snappy_hip_raw_decompress_split_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t unit_len, uint32_t segment_bytes,
+                                          uint64_t max_segments, uint64_t max_units, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result,
+                                          void* d_scratch, uint64_t scratch_bytes, void* stream)
+{
+    using namespace snappy_hip;
+    if (!split_params(unit_len, segment_bytes))
+        return fail(SNAPPY_HIP_ERR_ARG, "unit_len must be 0 or at least 256, segment_bytes 0 or a multiple of 64 of at least 128");
+    if (!d_result || (count && (!d_items || !d_out_len || !d_status))) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    max_segments = std::min(max_segments, kSplitMaxWork);
+    max_units = std::min(max_units, kSplitMaxWork);
+    const SplitLayout l = split_layout(count, max_segments, max_units);
+    if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_raw_decompress_split_scratch_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
+    uint64_t* seg_prefix = reinterpret_cast<uint64_t*>(scratch + l.seg_prefix);
+    uint64_t* unit_prefix = reinterpret_cast<uint64_t*>(scratch + l.unit_prefix);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(scratch + l.flags);
+    uint64_t* table = reinterpret_cast<uint64_t*>(scratch + l.table);
+    uint4* nodes = reinterpret_cast<uint4*>(scratch + l.nodes);
+    uint32_t* cuts = reinterpret_cast<uint32_t*>(scratch + l.cuts);
+    const auto* items = reinterpret_cast<const RawItem*>(d_items);
+    hipLaunchKernelGGL(raw_split_plan_kernel, dim3(1), dim3(1024), 0, st, items, count, unit_len, segment_bytes, max_segments, max_units, d_out_len,
+                       d_status, d_result, ctl, seg_prefix, unit_prefix, flags, cuts);
+    HIP_TRY(hipGetLastError());
+    if (count == 0) return SNAPPY_HIP_OK;
+    const uint32_t cap = range_grid_cap();
+    if (max_segments && max_units) {        // (else no item can be split: the serial step takes them all)
+        const uint32_t seg_grid = (uint32_t)std::min<uint64_t>(cap, max_segments), unit_grid = (uint32_t)std::min<uint64_t>(cap, max_units);
+        int rc = launch_counted(st, [&](uint32_t* counter) {
+            hipLaunchKernelGGL(raw_split_walk_kernel, dim3(seg_grid), dim3(64), 0, st, items, count, segment_bytes, ctl, seg_prefix, flags, table, nodes,
+                               counter);
+            return 0;
+        });
+        if (rc) return rc;
+        hipLaunchKernelGGL(raw_split_resolve_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, items, count, unit_len, segment_bytes, d_out_len,
+                           seg_prefix, unit_prefix, flags, table, nodes, cuts);
+        HIP_TRY(hipGetLastError());
+        rc = launch_counted(st, [&](uint32_t* counter) {
+            hipLaunchKernelGGL(raw_split_cuts_kernel, dim3(seg_grid), dim3(64), 0, st, items, count, unit_len, ctl, d_out_len, seg_prefix, unit_prefix,
+                               flags, nodes, cuts, counter);
+            return 0;
+        });
+        if (rc) return rc;
+        rc = launch_counted(st, [&](uint32_t* counter) {
+            hipLaunchKernelGGL(raw_split_units_kernel, dim3(unit_grid), dim3(64), 0, st, items, count, unit_len, ctl, d_out_len, unit_prefix, flags, cuts,
+                               counter);
+            return 0;
+        });
+        if (rc) return rc;
+    }
+    return launch_counted(st, [&](uint32_t* counter) {
+        hipLaunchKernelGGL(raw_split_serial_kernel, dim3(std::min(cap, count)), dim3(64), 0, st, items, count, d_out_len, d_status, flags, d_result,
+                           counter);
+        return 0;
+    });
 }
 
 // ---- checking without decoding (snappy_check.hpp) ----

@@ -7,7 +7,8 @@
 //   * decode: raw_decompress_kernel (persistent wavefronts, one counter, as decompress_ranges_kernel): a wavefront draws an
 //     item, reads its header and decodes the whole stream with K2's own decoder in its raw form (k2_decode_block<true>:
 //     literals of any length, 64-bit bounds against the stream, wide run-on copies).  Element boundaries of a raw stream cannot
-//     be found without parsing it, so ONE STREAM IS ONE WAVEFRONT'S WORK; the device is full only with thousands of items.
+//     be found without parsing it, so ONE STREAM IS ONE WAVEFRONT'S WORK here; the device is full only with thousands of items.
+//     (snappy_raw_split.hpp decodes one LARGE stream with many wavefronts, and shares this kernel's trip.)
 //   * compress: a FRAGMENT is block_size bytes of an item, compressed as one K1 block (own hash table, no reference across
 //     fragments -- what Google's compressor does with its 64 KiB fragments, so any decoder accepts the result).  The work unit
 //     is the pair (item, fragment), found from the exclusive prefix of the items' fragment counts by binary search.  Four
@@ -38,6 +39,55 @@ struct RawItem {               // must match snappy_hip_raw_item (include/snappy
     uint64_t dst_capacity;
 };
 
+// The descriptor and the header of item i and the item's verdict, by the rules every raw decoder shares: a null src or a
+// malformed header is INVALID with a length of 0, a stream or a length above kRawMaxLen is TOO_LARGE, a length above the
+// capacity (a null dst counts as 0) DST_TOO_SMALL, a length of 0 is OK iff nothing follows the header; for every other item
+// the verdict is `elements`, an expression over src, src_len, hdr, dst and length: its elements src[hdr, src_len) are to be
+// decoded into dst[0, length).  Declares those five, capacity and `uint32_t st` in the caller's scope.  uld / ubyte: uld64 /
+// uni when the whole wavefront reads ONE item (i wave-uniform, everything lands in scalar registers), ld64 / a plain cast
+// when every thread reads an item of its own.  A macro, so that raw_decompress_kernel's text -- and with it its generated
+// code, which tools/kernel_asm_diff.py holds to what it was measured with -- stays what it was while raw_split_plan_kernel and
+// raw_split_serial_kernel (snappy_raw_split.hpp) read the same rules.
+#define SNAPPY_RAW_ITEM_VERDICT(items, i, uld, ubyte, elements)                                                                \
+    const uint8_t* src = load_global_ptr(&items[i].src);                                                                       \
+    uint8_t* dst = load_global_ptr(&items[i].dst);                                                                             \
+    const uint64_t src_len = uld(reinterpret_cast<const uint8_t*>(&items[i].src_len));                                         \
+    const uint64_t capacity = dst ? uld(reinterpret_cast<const uint8_t*>(&items[i].dst_capacity)) : 0;                         \
+    /* the header: a varint32 as Google's decoder reads it -- at most 5 bytes, the fifth below 16, inside the stream */         \
+    uint32_t length = 0, hdr = 0;                                                                                              \
+    if (src)                                                                                                                   \
+        for (uint32_t k = 0; k < 5 && k < src_len; ++k) {                                                                      \
+            const uint32_t c = ubyte((uint32_t)src[k]);                                                                        \
+            if (k == 4 && c >= 16u) break;                                                                                     \
+            length |= (c & 0x7fu) << (7u * k);                                                                                 \
+            if (c < 0x80u) {                                                                                                   \
+                hdr = k + 1;                                                                                                   \
+                break;                                                                                                         \
+            }                                                                                                                  \
+        }                                                                                                                      \
+    uint32_t st;                                                                                                               \
+    if (hdr == 0) {                                                                                                            \
+        st = kBlockInvalid;                                                                                                    \
+        length = 0;                                                                                                            \
+    } else if (src_len > kRawMaxLen || length > kRawMaxLen) {                                                                  \
+        st = kRawTooLarge;                                                                                                     \
+    } else if (length > capacity) {                                                                                            \
+        st = kRawDstTooSmall;                                                                                                  \
+    } else if (length == 0) {                                                                                                  \
+        st = src_len == hdr ? kBlockOk : kBlockInvalid; /* nothing may follow the header */                                    \
+    } else {                                                                                                                   \
+        st = (elements);                                                                                                       \
+    }
+
+// One item decoded by ONE wavefront, verdict and length stored: a trip of raw_decompress_kernel and of the split call's serial
+// step.  i is wave-uniform; every lane of the wavefront runs it.
+#define SNAPPY_RAW_DECODE_ITEM(items, i, out_len, status, stage, lane)                                                         \
+    SNAPPY_RAW_ITEM_VERDICT(items, i, uld64, uni, k2_decode_block<true>(src, src_len, hdr, dst, length, stage))                \
+    if (lane == 0) {                                                                                                           \
+        status[i] = st;                                                                                                        \
+        out_len[i] = length;                                                                                                   \
+    }
+
 __global__ __launch_bounds__(64) void raw_decompress_kernel(const RawItem* __restrict__ items, uint32_t count, uint64_t* __restrict__ out_len,
                                                             uint32_t* __restrict__ status, uint32_t* next_item)
 {
@@ -48,39 +98,7 @@ __global__ __launch_bounds__(64) void raw_decompress_kernel(const RawItem* __res
     for (;;) {
         const uint32_t i = draw_work(next_item, lane);
         if (i >= count) break;
-        const uint8_t* src = load_global_ptr(&items[i].src);
-        uint8_t* dst = load_global_ptr(&items[i].dst);
-        const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));
-        const uint64_t capacity = dst ? uld64(reinterpret_cast<const uint8_t*>(&items[i].dst_capacity)) : 0;
-        // the header: a varint32 as Google's decoder reads it -- at most 5 bytes, the fifth below 16, inside the stream
-        uint32_t length = 0, hdr = 0;
-        if (src)
-            for (uint32_t k = 0; k < 5 && k < src_len; ++k) {
-                const uint32_t c = uni((uint32_t)src[k]);
-                if (k == 4 && c >= 16u) break;
-                length |= (c & 0x7fu) << (7u * k);
-                if (c < 0x80u) {
-                    hdr = k + 1;
-                    break;
-                }
-            }
-        uint32_t st;
-        if (hdr == 0) {
-            st = kBlockInvalid;
-            length = 0;
-        } else if (src_len > kRawMaxLen || length > kRawMaxLen) {
-            st = kRawTooLarge;
-        } else if (length > capacity) {
-            st = kRawDstTooSmall;
-        } else if (length == 0) {
-            st = src_len == hdr ? kBlockOk : kBlockInvalid;          // nothing may follow the header
-        } else {
-            st = k2_decode_block<true>(src, src_len, hdr, dst, length, stage);
-        }
-        if (lane == 0) {
-            status[i] = st;
-            out_len[i] = length;
-        }
+        SNAPPY_RAW_DECODE_ITEM(items, i, out_len, status, stage, lane)
         __syncthreads();
     }
 }

@@ -5,7 +5,7 @@
  * snappy_decompress_dpu (dpu_snappy.c:169-172, :189-192).  Without -d the host CPU codec runs,
  * as in the reference.  -d never falls back to the CPU.
  *
- *   dpu_snappy [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] [-c] [-R] [-S [<unit_len>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
  *   dpu_snappy [-d] [-R] -T -i <input_file>
  */
 #include <getopt.h>
@@ -23,11 +23,12 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "**DEBUG BUILD**\n");
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
-	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] [-R] -T -i <input_file>\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
+	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
 	fprintf(stderr, "r: decompress only <length> bytes from uncompressed byte <offset> of the input\n");
@@ -111,8 +112,25 @@ int main(int argc, char **argv)
 	unsigned long long keep_len = 0;
 	const char *tail_path = NULL;
 	int use_check = 0;
-	while ((opt = getopt(argc, argv, "dcRTb:g:i:o:r:w:t:a:")) != -1) {
+	int use_split = 0;
+	unsigned long split_unit = 0;
+	while ((opt = getopt(argc, argv, "dcRTS::b:g:i:o:r:w:t:a:")) != -1) {
 		switch (opt) {
+		case 'S': {                  /* -S, -S<unit_len> or -S <unit_len> */
+			const char *arg = optarg;
+			if (!arg && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
+				arg = argv[optind++];
+			if (arg) {
+				char *rest = NULL;
+				split_unit = strtoul(arg, &rest, 10);
+				if (rest == arg || *rest != '\0' || split_unit < 256 || split_unit > 0xffffffffUL) {
+					fprintf(stderr, "-S wants <unit_len> in bytes, at least 256, got '%s'\n", arg);
+					return -2;
+				}
+			}
+			use_split = 1;
+			break;
+		}
 		case 'T': use_check = 1; break;
 		case 't': {                  /* keep only the first keep_len uncompressed bytes */
 			char *rest = NULL;
@@ -177,6 +195,10 @@ int main(int argc, char **argv)
 	}
 	if (raw && (use_range || use_write)) {
 		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
+		return -2;
+	}
+	if (use_split && (!raw || compress || use_check)) {
+		fprintf(stderr, "-S splits the decoding of one raw Snappy stream: it goes with -R and not with -c or -T\n");
 		return -2;
 	}
 	const int use_resize = use_keep || tail_path;
@@ -254,7 +276,9 @@ int main(int argc, char **argv)
 			output.buffer = NULL;
 			output.curr = NULL;
 			output.max = ULONG_MAX;
-			st = compress ? snappy_compress_raw_gpu(&input, &output, (uint32_t)block_size, &rt) : snappy_decompress_raw_gpu(&input, &output, &rt);
+			st = compress    ? snappy_compress_raw_gpu(&input, &output, (uint32_t)block_size, &rt)
+			     : use_split ? snappy_decompress_raw_split_gpu(&input, &output, (uint32_t)split_unit, &rt)
+			                 : snappy_decompress_raw_gpu(&input, &output, &rt);   /* (host mode ignores -S) */
 		} else {
 			if (compress)
 				setup_compression(&input, &output, &rt);

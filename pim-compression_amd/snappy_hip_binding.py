@@ -118,6 +118,13 @@ def lib():
                                         ctypes.POINTER(HostBufferContext), ctypes.POINTER(ProgramRuntime)]
         L.snappy_hip_raw_decompress_batch.restype = ctypes.c_int
         L.snappy_hip_raw_decompress_batch.argtypes = [vp, u32, vp, vp, vp]
+        L.snappy_hip_raw_decompress_split_scratch_bytes.restype = u64
+        L.snappy_hip_raw_decompress_split_scratch_bytes.argtypes = [u32, u32, u32, u64, u64]
+        L.snappy_hip_raw_decompress_split_batch.restype = ctypes.c_int
+        L.snappy_hip_raw_decompress_split_batch.argtypes = [vp, u32, u32, u32, u64, u64, vp, vp, vp, vp, u64, vp]
+        L.snappy_decompress_raw_split_gpu.restype = ctypes.c_int
+        L.snappy_decompress_raw_split_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                                      ctypes.POINTER(ProgramRuntime)]
         L.snappy_hip_raw_compress_bound.restype = u64
         L.snappy_hip_raw_compress_bound.argtypes = [u64, u32]
         L.snappy_hip_raw_compress_scratch_bytes.restype = u64
@@ -502,6 +509,28 @@ def raw_decompress_batch(d_items, count, d_out_len, d_status):
            "snappy_hip_raw_decompress_batch")
 
 
+def raw_decompress_split_scratch_bytes(count, unit_len, segment_bytes, max_segments, max_units):
+    """Scratch of snappy_hip_raw_decompress_split_batch (0 for a bad unit_len or segment_bytes)."""
+    return int(lib().snappy_hip_raw_decompress_split_scratch_bytes(count, unit_len, segment_bytes, max_segments, max_units))
+
+
+def raw_decompress_split_batch(d_items, count, unit_len, segment_bytes, max_segments, max_units, d_out_len, d_status, d_result, d_scratch=None):
+    """Enqueue snappy_hip_raw_decompress_split_batch on the current stream: raw_decompress_batch with every large item decoded by
+    many wavefronts where it is built from independent pieces of unit_len output bytes (0 = 65,536), serially where not.
+    segment_bytes: 0 = the default (16 KiB); max_segments / max_units: what the scratch is sized for.  d_result: device int32 tensor of
+    four (split, small, fallen back, 0).  d_scratch: 256-byte aligned device uint8 tensor (default: a fresh one).  Nothing is
+    synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(raw_decompress_split_scratch_bytes(count, unit_len, segment_bytes, max_segments, max_units), 256),
+                                dtype=torch.uint8, device=d_result.device)
+    _check(lib().snappy_hip_raw_decompress_split_batch(d_items.data_ptr() if count else None, count, unit_len, segment_bytes, max_segments, max_units,
+                                                       d_out_len.data_ptr() if count else None, d_status.data_ptr() if count else None,
+                                                       d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(), _stream_handle(torch)),
+           "snappy_hip_raw_decompress_split_batch")
+    return d_scratch
+
+
 def raw_compress_bound(src_len, block_size):
     """A dst_capacity that always suffices for an item of src_len bytes (0 for a bad block size)."""
     return int(lib().snappy_hip_raw_compress_bound(src_len, block_size))
@@ -732,6 +761,11 @@ def check_host(stream):
     rep, rt = CheckReport(), ProgramRuntime()
     st = lib().snappy_check_gpu(ctypes.byref(inp), ctypes.byref(rep), ctypes.byref(rt))
     return st, rep.as_dict(), rt.as_dict()
+
+
+def raw_decompress_split_host(stream, unit_len=0, out_capacity=None):
+    """snappy_decompress_raw_split_gpu on a whole raw Snappy stream held in host memory -> (status, plaintext, runtime dict)."""
+    return _raw_host(lambda i, o, r: lib().snappy_decompress_raw_split_gpu(i, o, unit_len, r), stream, out_capacity)
 
 
 def check_raw_host(stream):
