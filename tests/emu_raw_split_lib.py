@@ -34,6 +34,8 @@ def lib():
         L.emu_raw_split_dst_fill.restype = ctypes.c_uint
         L.emu_raw_decompress_split.restype = ctypes.c_int
         L.emu_raw_decompress_split.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u64, u64, vp, vp, vp, vp, u32]
+        L.emu_raw_decompress_split_traced.restype = ctypes.c_int
+        L.emu_raw_decompress_split_traced.argtypes = L.emu_raw_decompress_split.argtypes + [vp, vp, vp, vp, u64, vp, u64]
         _LIB = L
     return _LIB
 
@@ -49,12 +51,41 @@ def limits(items, unit_len, segment_bytes):
     return segs, units
 
 
-def decompress_split(items, unit_len=65536, segment_bytes=65536, max_segments=None, max_units=None, grid=3):
+FLAG_CLASS, FLAG_FALLBACK, CLASS_SPLIT = 3, 4, 2       # an item's flag word (csrc/snappy_raw_split.hpp)
+
+
+def decompress_split(items, unit_len=65536, segment_bytes=65536, max_segments=None, max_units=None, grid=3, trace=False):
     """items as emu_raw_lib.Batch takes them -> (rc, Batch); Batch.result holds the four result words.  rc 100 = a kernel wrote
-    in front of a window.  Writes behind a window fault.  Limits left out hold the whole batch."""
+    in front of a window, 101 = behind the scratch.  Writes behind a window fault.  Limits left out hold the whole batch.
+    trace: the Batch also gets what steps 1-4 left in the scratch: plan_flags[i] and flags[i] (the item's flag word after step
+    1 and after step 4), cuts[i] (its units + 1 cuts) and nodes[i] (one (entry, landing, output base) or None per segment); the
+    last two are None unless the plan classed the item split inside the limits."""
     b = emu_raw_lib.Batch(items)
     b.result = np.full(5, 0x77, dtype=np.uint32)
     need_s, need_u = limits(items, unit_len, segment_bytes)
+    if trace:
+        n = b.n
+        plan_flags, flags, count = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint32), np.zeros(2 * n + 2, np.uint32)
+        cuts, nodes = np.zeros(need_u + n + 1, np.uint32), np.zeros(3 * need_s + 3, np.uint32)
+        rc = lib().emu_raw_decompress_split_traced(
+            b.src.ctypes.data, b.real_len.ctypes.data, b.src_len.ctypes.data, b.capacity.ctypes.data, b.flags.ctypes.data, n, unit_len, segment_bytes,
+            need_s if max_segments is None else max_segments, need_u if max_units is None else max_units, b.out.ctypes.data, b.out_len.ctypes.data,
+            b.status.ctypes.data, b.result.ctypes.data, grid, plan_flags.ctypes.data, flags.ctypes.data, count.ctypes.data, cuts.ctypes.data,
+            need_u + n, nodes.ctypes.data, 3 * need_s)
+        assert rc >= 0, "the trace's arrays are too small"
+        b.plan_flags, b.step4_flags = [int(x) for x in plan_flags[:n]], [int(x) for x in flags[:n]]
+        b.cuts, b.nodes = [None] * n, [None] * n
+        c_at = n_at = 0
+        for i in range(n):
+            nc, nn = int(count[2 * i]), int(count[2 * i + 1])
+            if nc:
+                b.cuts[i] = [int(x) for x in cuts[c_at:c_at + nc]]
+                trip = nodes[n_at:n_at + 3 * nn].reshape(nn, 3)
+                b.nodes[i] = [None if int(t[0]) == 0xffffffff else (int(t[0]), int(t[1]), int(t[2])) for t in trip]
+            c_at += nc
+            n_at += 3 * nn
+        assert int(b.result[4]) == 0x77 and int(b.status[b.n]) == 0x55 and int(b.out_len[b.n]) == 0x5A5A5A5A5A5A5A5A
+        return rc, b
     rc = lib().emu_raw_decompress_split(b.src.ctypes.data, b.real_len.ctypes.data, b.src_len.ctypes.data, b.capacity.ctypes.data, b.flags.ctypes.data,
                                         b.n, unit_len, segment_bytes, need_s if max_segments is None else max_segments,
                                         need_u if max_units is None else max_units, b.out.ctypes.data, b.out_len.ctypes.data, b.status.ctypes.data,

@@ -61,6 +61,30 @@ def intact_containers():
     return out
 
 
+PLANNER_TRIP_CONTAINERS = 1031
+
+
+def planner_trip_containers():
+    """[(stream, offsets, total_len, block_size)]: more containers than one trip of check_plan_kernel (1,024) -- one-block
+    containers of at most 64 bytes, every eleventh damaged (its block starts with a copy: nothing to copy from), and as
+    container 1024, the first of the second trip, one of four blocks whose block 2 is damaged."""
+    kinds = []
+    for k in range(5):
+        stream, _ = datagen.element_stream(40 + 5 * k, 64, 900 + k, k % 4)
+        total, bs, offs = _offsets(stream)
+        bad = bytearray(stream)
+        bad[offs[0] + 4] = 0xFF
+        kinds.append(((stream, offs, total, bs), (bytes(bad), offs, total, bs)))
+    stream, _ = datagen.element_stream(3 * 64 + 20, 64, 910, 0)
+    total, bs, offs = _offsets(stream)
+    bad = bytearray(stream)
+    bad[offs[2] + 4] = 0xFF
+    out = [kinds[i % 5][i % 11 == 7] for i in range(PLANNER_TRIP_CONTAINERS)]
+    out[1024] = (bytes(bad), offs, total, bs)
+    assert len(offs) == 4
+    return out
+
+
 def intact_jobs():
     jobs = []
     for name, stream, _ in intact_containers():

@@ -119,6 +119,23 @@ def body_batch():
     assert rcode == 0 and results == [[ec.OK if w[0] != ec.OUT_OF_BOUNDS else w[0], 0, ec.NONE, 0] for w in want_result]
 
 
+def body_planner_trips():
+    conts = kc.planner_trip_containers()
+    k2 = {}
+    for stream, offs, total, bs in conts:
+        if stream not in k2:
+            step("k2 on a container of", len(offs))
+            k2[stream] = _k2_statuses(stream, total, bs, offs)
+    want = [k2[c[0]] for c in conts]
+    assert len(conts) > 1024 and want[1024] == [ec.OK, ec.OK, ec.INVALID, ec.OK], want[1024]
+    assert sum(w == [ec.INVALID] for w in want) > 90 and sum(w == [ec.INVALID] for w in want[1025:]) > 0
+    step("check", len(conts), "containers")
+    rcode, results, statuses = ec.check_blocks([ec.Container(s, offs, total, bs) for s, offs, total, bs in conts], grid=3)
+    assert rcode == 0
+    for i, w in enumerate(want):
+        assert statuses[i] == w and results[i] == ec.fold(w), (i, statuses[i], results[i], w)
+
+
 # ---- raw ----
 def _raw_decode(s):
     """the emulated decoder's (status, out_len) at full capacity, or None where it cannot be run (a length nobody can allocate)"""
@@ -218,7 +235,7 @@ def body_fuzz():
     assert ok + invalid == 500 and ok >= 50 and invalid >= 50, (ok, invalid)
 
 
-BODIES = {f.__name__[5:]: f for f in (body_blocks, body_batch, body_raw, body_fuzz)}
+BODIES = {f.__name__[5:]: f for f in (body_blocks, body_batch, body_raw, body_fuzz, body_planner_trips)}
 
 
 def in_child(name, *args):
@@ -245,6 +262,12 @@ def test_batch_of_mixed_containers_with_fewer_wavefronts_than_blocks():
     damaged one and five malformed descriptors in one call; without status arrays, with null ones, with all of them; counts
     and first-bad indices against a fold over K2's statuses; junk in and guards beside every array."""
     in_child("batch")
+
+
+def test_more_containers_than_one_trip_of_the_planner():
+    """1,031 containers, the 1,025th with four blocks of which one is damaged, damaged one-block containers on both sides of
+    the planner's trip boundary: results and statuses against K2 per block."""
+    in_child("planner_trips")
 
 
 def test_raw_streams_get_the_decoders_verdict_and_length():

@@ -156,6 +156,16 @@ def test_block_statuses_and_results_against_k2_in_one_call(shb):
     assert call.results == first
 
 
+def test_more_containers_than_one_trip_of_the_planner(shb):
+    """1,031 containers (k2_window_cases.planner_trip_containers), the 1,025th with four blocks of which one is damaged:
+    results and statuses against K2 per block."""
+    conts = kc.planner_trip_containers()
+    call = Call(shb, conts)
+    want = call.k2()
+    assert len(conts) > 1024 and want[1024] == [OK, OK, INVALID, OK] and sum(w == [INVALID] for w in want) > 90
+    call.run().compare(want)
+
+
 def test_malformed_descriptors_are_out_of_bounds_and_not_read(shb):
     import torch
     name, stream, _ = kc.intact_containers()[2]
@@ -297,6 +307,21 @@ def test_raw_vectors_and_fixtures_against_the_decoder(shb):
         assert (st, n) == (0, len(rc.fixture_plain(name))) and rt["run"] > 0, name
     s = rc.fixture_stream("terror2")
     assert shb.check_raw_host(s[:len(s) // 2])[0] == 1 and shb.check_raw_host(b"")[:2] == (1, 0)
+
+
+def test_raw_check_of_damaged_rich_streams_against_the_independent_decoder(shb):
+    """600 seeded mutations of streams no greedy compressor writes (tests/raw_split_cases.damaged_rich_streams): the check's
+    (status, out_len) equals raw_cases.expect, the format's CPU statement, on every one."""
+    import raw_split_cases as sc
+    from test_gpu_raw import Batch
+    items = sc.damaged_rich_streams()
+    want = [rc.expect(s, n)[:2] for s, n in items]
+    assert len(items) == 600 and [w[0] for w in want].count(rc.OK) >= 100 and [w[0] for w in want].count(rc.INVALID) >= 100
+    chk = Batch([(s, 0) for s, _ in items])
+    shb.raw_check_batch(shb.make_raw_items([(e[0], e[1], 0, 0) for e in chk.entries]), chk.n, chk.d_out_len, chk.d_status)
+    chk.fetch()
+    assert list(zip(chk.status, chk.out_len))[:chk.n] == want, [(i, chk.status[i], chk.out_len[i], w) for i, w in enumerate(want)
+                                                                  if (chk.status[i], chk.out_len[i]) != w][:5]
 
 
 def test_cli_check_on_the_device(shb, tmp_path):

@@ -123,6 +123,18 @@ def test_gpu_raw_decode_fixtures_and_vectors_in_one_batch(shb):
     assert sorted(set(b.status[:b.n])) == [rc.OK, rc.INVALID, rc.DST_TOO_SMALL]
 
 
+def test_gpu_raw_decode_damaged_rich_streams_against_the_independent_decoder(shb):
+    """600 seeded mutations of streams no greedy compressor writes (tests/raw_split_cases.damaged_rich_streams) in one launch:
+    (status, out_len) equals raw_cases.expect, accepted bytes are decode_raw's, nothing behind dst[length)."""
+    import raw_split_cases as sc
+    items = sc.damaged_rich_streams()
+    verdicts = [rc.expect(s, n)[0] for s, n in items]
+    assert len(items) == 600 and verdicts.count(rc.OK) >= 100 and verdicts.count(rc.INVALID) >= 100
+    b = gpu_decompress(shb, items)
+    for i, (s, n) in enumerate(items):
+        check_decoded(b, i, s, n)
+
+
 def test_gpu_raw_decode_alone_and_limits(shb):
     import torch
     lit = rc.intact_vectors()["literal_65537"]

@@ -3,7 +3,8 @@ hand-built, mixed-batch, damage and limit cases of tests/test_raw_split_emulated
 every dst, under the default grid and under SNAPPY_HIP_K2_WAVES=3 (three wavefronts for every persistent kernel); the
 drop-in call and one CLI round trip with -S.  The fixtures (at most 482 KB) with segments of 128 to 4,096 bytes are the
 smallest shapes with many segments, several units and every case of the resolve step.  All comparisons are exact: the
-plaintext, and the serial call (snappy_hip_raw_decompress_batch) on the same items."""
+plaintext, and the serial call (snappy_hip_raw_decompress_batch) on the same items.  The result words of the model-driven
+tests come from tests/raw_split_cases.model, never from the device."""
 import random
 
 import pytest
@@ -11,6 +12,7 @@ import pytest
 import datagen
 import emu_raw_split_lib as es
 import raw_cases as rc
+import raw_split_cases as sc
 import test_raw_split_emulated as cases
 from conftest import golden_bytes
 from test_gpu_raw import FILL, Batch, gpu_compress, gpu_decompress, shb, _cli   # noqa: F401  (shb: the module's fixture)
@@ -68,9 +70,69 @@ def test_gpu_split_fixtures_without_a_fallback(shb, grid, segment_bytes):
 
 
 def test_gpu_split_defaults(shb):
+    """the defaults (units of 65,536, segments of 16,384): plrabn12, and a fragment-built stream of elements no greedy compressor
+    writes, 5 units and 17 segments long"""
     plain = rc.fixture_plain("plrabn12")
-    b = gpu_split(shb, [(rc.fixture_stream("plrabn12"), len(plain))], 0, 0)
-    assert b.result == [1, 0, 0, 0] and b.status[0] == rc.OK and b.window(0) == plain
+    s, p = sc.fragment_stream(4 * 65536 + 12345, 65536, 77, 2)
+    m = sc.model(s, 65536, 16384)
+    assert m.words == sc.SPLIT and m.units == 5 and m.segments > 8 and set(range(8)) <= set(m.nodes)
+    b = gpu_split(shb, [(rc.fixture_stream("plrabn12"), len(plain)), (s, len(p))], 0, 0)
+    assert b.result == [2, 0, 0, 0] and b.status[:2] == [rc.OK, rc.OK] and b.window(0) == plain and b.window(1) == p
+
+
+def test_gpu_split_fragment_built_streams_never_fall_back(shb, grid):
+    """tests/raw_split_cases.fragment_built_calls: exactly [n, 0, 0, 0] and the plaintext"""
+    for unit_len, segment_bytes, items in sc.fragment_built_calls():
+        b = gpu_split(shb, [(s, len(p)) for s, p in items], unit_len, segment_bytes)
+        assert b.result == [len(items), 0, 0, 0], (unit_len, segment_bytes, b.result)
+        for i, (s, p) in enumerate(items):
+            assert (b.status[i], b.out_len[i]) == (rc.OK, len(p)) and b.window(i) == p, (unit_len, i)
+
+
+@pytest.fixture(scope="module")
+def model_batches():
+    """computed once for both grids: [(config, items, plaintexts, the model's result words)]"""
+    out = []
+    for config in sc.CONFIGS:
+        batch = sc.model_batch(config)
+        models = [sc.model(s, *config) for _, s, _ in batch]
+        sc.assert_covers(models)
+        out.append((config, [(s, len(p) + i % 3) for i, (_, s, p) in enumerate(batch)], [p for _, _, p in batch], sc.batch_words(models)))
+    return out
+
+
+@pytest.mark.parametrize("k", range(len(sc.CONFIGS)))
+def test_gpu_split_any_valid_stream_gets_the_models_words(shb, grid, model_batches, k):
+    """About a hundred valid items in one call; the result words are those of the model of steps 2-4 (a wrong walk, resolve or
+    cut shows here and nowhere else); status, length and bytes are decode_raw's and the serial call's."""
+    config, items, plains, words = model_batches[k]
+    b = gpu_split(shb, items, *config)
+    assert b.result == words, (b.result, words)
+    same_as_serial(shb, items, b, plains)
+
+
+def test_gpu_split_stream_ends(shb, grid):
+    ends = sc.stream_ends()
+    streams = [s for pair in ends.values() for s in pair] + list(sc.hostile_ends().values())
+    items = [(s, 768) for s in streams]
+    b = gpu_split(shb, items, 256, 128)
+    assert b.result == [len(ends), 0, len(streams) - len(ends), 0], b.result
+    same_as_serial(shb, items, b)
+    for i, s in enumerate(streams):
+        st, n, plain = rc.expect(s)
+        assert (b.status[i], b.out_len[i]) == (st, n) and (st != rc.OK or b.window(i) == plain), i
+    assert [rc.expect(s)[0] for s in streams].count(rc.OK) == len(ends)
+
+
+def test_gpu_split_more_items_than_one_trip_of_the_planner(shb, grid):
+    batch = sc.planner_trip_items()
+    models = [sc.model(s, 256, 128) for s, _ in batch]
+    items = [(s, len(p)) for s, p in batch]
+    for max_segments, max_units in sc.planner_trip_limits(models):
+        b = gpu_split(shb, items, 256, 128, max_segments=max_segments, max_units=max_units)
+        assert b.result == sc.batch_words(models, max_segments, max_units), (max_segments, max_units, b.result)
+        for i, (s, p) in enumerate(batch):
+            assert (b.status[i], b.out_len[i]) == (rc.OK, len(p)) and b.window(i) == p, (max_segments, max_units, i)
 
 
 def test_gpu_split_fixtures_without_independent_units_fall_back(shb, grid):
@@ -121,6 +183,17 @@ def test_gpu_split_flipped_bytes_get_the_serial_verdict(shb):
         items.append((s[:at] + bytes([s[at] ^ (1 << rnd.randrange(8))]) + s[at + 1:], n))
     for segment_bytes in (128, 4096):
         same_as_serial(shb, items, gpu_split(shb, items, 65536, segment_bytes))
+
+
+def test_gpu_split_damaged_rich_streams_against_the_independent_decoder(shb, grid):
+    """the 600 mutations of test_gpu_raw's test through the split call: raw_cases.expect's verdict, decode_raw's bytes"""
+    from test_gpu_raw import check_decoded
+    items = sc.damaged_rich_streams()
+    verdicts = [rc.expect(s, n)[0] for s, n in items]
+    b = gpu_split(shb, items, 256, 128)
+    for i, (s, n) in enumerate(items):
+        check_decoded(b, i, s, n)
+    assert b.result[0] > 0 and b.result[2] >= verdicts.count(rc.INVALID) >= 100 and sum(b.result) == len(items), b.result
 
 
 def test_gpu_split_items_beyond_the_limits_fall_back(shb, grid):

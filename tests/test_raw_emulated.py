@@ -139,6 +139,35 @@ def body_k2_window_vectors():
         decode_alone(name, rc.varint(out_len) + stream[at + 4:at + 4 + size])
 
 
+def body_damaged_rich_streams():
+    """600 mutations of streams no greedy compressor writes: the decoder, the check and the split call against the format's CPU
+    statement, which shares no code with any of them"""
+    import emu_check_lib as ec
+    import emu_raw_split_lib as es
+    import raw_split_cases as sc
+    items = sc.damaged_rich_streams()
+    want = [rc.expect(s, n) for s, n in items]
+    verdicts = [w[0] for w in want]
+    print("expect's verdicts", verdicts.count(rc.OK), verdicts.count(rc.INVALID), flush=True)
+    assert len(items) == 600 and verdicts.count(rc.OK) >= 100 and verdicts.count(rc.INVALID) >= 100 and set(verdicts) == {rc.OK, rc.INVALID}
+    step("decode", len(items))
+    r, b = er.decompress(items, grid=3)
+    assert r == 0
+    for i, (s, n) in enumerate(items):
+        step("item", i)
+        check_decoded(b, i, s, n)
+    step("check")
+    assert ec.raw_check([s for s, _ in items], grid=3) == [w[:2] for w in want]
+    step("split")
+    r, sp = es.decompress_split(items, 256, 128, grid=3)
+    assert r == 0
+    for i, (s, n) in enumerate(items):
+        step("split item", i)
+        check_decoded(sp, i, s, n)
+    res = [int(x) for x in sp.result[:4]]
+    assert res[0] > 0 and res[2] >= verdicts.count(rc.INVALID) and sum(res) == len(items), res
+
+
 # ---- compress ----
 def want_raw(plain, bs):
     return rc.trs.convert(oracle.compress(plain, bs))
@@ -221,7 +250,7 @@ def body_compress_goldens():
 
 
 BODIES = {f.__name__[5:]: f for f in (body_fixtures, body_intact_vectors, body_damaged_vectors, body_capacity, body_mixed_batch,
-                                      body_k2_window_vectors, body_compress, body_compress_max_fragments, body_compress_goldens)}
+                                      body_k2_window_vectors, body_damaged_rich_streams, body_compress, body_compress_max_fragments, body_compress_goldens)}
 
 
 def in_child(name, *args):
@@ -260,6 +289,12 @@ def test_decode_mixed_batch_with_fewer_wavefronts_than_items():
 
 def test_decode_k2_window_vectors_as_raw_streams():
     in_child("k2_window_vectors")
+
+
+def test_decode_check_and_split_of_damaged_rich_streams_against_the_independent_decoder():
+    """(status, out_len) of snappy_hip_raw_decompress_batch, _raw_check_batch and _raw_decompress_split_batch equal
+    raw_cases.expect on every one of 600 mutated streams, and accepted bytes are decode_raw's."""
+    in_child("damaged_rich_streams")
 
 
 @pytest.mark.parametrize("form", [3, 2])

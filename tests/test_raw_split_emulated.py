@@ -2,7 +2,9 @@
 on the lockstep wave emulator, the six of them in the order snappy_hip_raw_decompress_split_batch enqueues them.  Every dst is
 a window of exactly its capacity between inaccessible pages and every src ends at one, so a byte written outside a window or
 read behind a stream is a fault -- which is why every body below runs in a child process that names the step it is on.  The
-oracle is the plaintext; status and length must be what the serial kernel (emu_raw_lib.decompress) gives the same items."""
+oracle is the plaintext; status and length must be what the serial kernel (emu_raw_lib.decompress) gives the same items.
+A mistake in steps 2-4 costs fallbacks, never a byte, so the result words, the cuts and the nodes are held to a model of those
+steps in plain Python (tests/raw_split_cases.py), on streams of elements that no greedy compressor writes."""
 import os
 import random
 import subprocess
@@ -14,6 +16,7 @@ import datagen
 import emu_raw_lib as er
 import emu_raw_split_lib as es
 import raw_cases as rc
+import raw_split_cases as sc
 from conftest import golden_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,7 +49,7 @@ def same_as_serial(items, b, plains=None):
 
 def run(items, unit_len, segment_bytes, **kw):
     r, b = es.decompress_split(items, unit_len, segment_bytes, **kw)
-    assert r == 0, "a kernel wrote in front of a window"
+    assert r == 0, "a kernel wrote in front of a window (100) or behind the scratch (101): %d" % r
     return b
 
 
@@ -197,8 +200,86 @@ def body_limits():
     assert r == 0 and result(b) == [0, 0, 0, 0]
 
 
+# ---- steps 2-4 against the model (tests/raw_split_cases.py) ----
+def same_as_model(b, models, limits=(None, None)):
+    """a traced batch of VALID items against the model: the result words; the plan's classes; no mark from steps 2-4; for every
+    split-class item inside the limits its cuts in every slot (NONE where no element starts, src_len at the end) and its nodes"""
+    assert result(b) == sc.batch_words(models, *limits), (result(b), sc.batch_words(models, *limits))
+    traced = 0
+    for i, m in enumerate(models):
+        step("trace of item", i)
+        assert m.valid and (b.plan_flags[i] & es.FLAG_CLASS == es.CLASS_SPLIT) == m.split_class and b.plan_flags[i] >> 8 == m.hdr, i
+        if b.cuts[i] is None:
+            assert not m.split_class or b.plan_flags[i] & es.FLAG_FALLBACK, i
+            continue
+        traced += 1
+        assert not b.step4_flags[i] & es.FLAG_FALLBACK, i
+        assert b.cuts[i] == m.cuts, (i, [(k, c, w) for k, (c, w) in enumerate(zip(b.cuts[i], m.cuts)) if c != w][:4])
+        want = [m.nodes.get(s) for s in range(m.segments)]
+        assert b.nodes[i] == want, (i, [(s, g, w) for s, (g, w) in enumerate(zip(b.nodes[i], want)) if g != w][:4])
+    return traced
+
+
+def body_fragment_built():
+    for unit_len, segment_bytes, items in sc.fragment_built_calls():
+        step("fragment-built, units of", unit_len, "segments of", segment_bytes)
+        b = run([(s, len(p)) for s, p in items], unit_len, segment_bytes, trace=True)
+        assert result(b) == [len(items), 0, 0, 0], result(b)
+        for i, (s, p) in enumerate(items):
+            assert (int(b.status[i]), int(b.out_len[i])) == (rc.OK, len(p)) and b.window(i) == p, i
+        assert same_as_model(b, [sc.model(s, unit_len, segment_bytes) for s, _ in items]) == len(items)
+
+
+def body_model_batch(k):
+    config = sc.CONFIGS[k]
+    batch = sc.model_batch(config)
+    models = [sc.model(s, *config) for _, s, _ in batch]
+    sc.assert_covers(models)
+    items = [(s, len(p) + i % 3) for i, (_, s, p) in enumerate(batch)]
+    step("model batch", config, "of", len(items))
+    b = run(items, *config, trace=True)
+    same_as_model(b, models)
+    same_as_serial(items, b, [p for _, _, p in batch])
+
+
+def body_stream_ends():
+    ends = sc.stream_ends()
+    streams = [s for pair in ends.values() for s in pair] + list(sc.hostile_ends().values())
+    models = [sc.model(s, 256, 128) for s in streams]
+    items = [(s, 768) for s in streams]
+    step("stream ends")
+    b = run(items, 256, 128, grid=2, trace=True)
+    valid = [m for m in models if m.valid]
+    assert len(valid) == len(ends) and result(b) == [len(valid), 0, len(streams) - len(valid), 0], result(b)
+    want = same_as_serial(items, b)
+    for i, (s, m) in enumerate(zip(streams, models)):
+        step("end", i)
+        st, n, plain = rc.expect(s)
+        assert (int(want.status[i]), int(want.out_len[i])) == (st, n) and (st == rc.OK) == m.valid, i
+        assert m.split_class and m.entry_offsets[m.segments - 2] < sc.ZONE           # (the last segment's lanes and a lookup end on it)
+        assert b.nodes[i] == [m.nodes.get(k) for k in range(m.segments)], (i, b.nodes[i])
+        if m.valid:
+            assert b.window(i) == plain and b.cuts[i] == m.cuts and not b.step4_flags[i] & es.FLAG_FALLBACK, i
+        else:                                             # no chain: step 3 marks it, no cut is ever written
+            assert b.step4_flags[i] & es.FLAG_FALLBACK and b.cuts[i] == [sc.NONE] * 4, (i, b.cuts[i])
+
+
+def body_planner_trips():
+    batch = sc.planner_trip_items()
+    models = [sc.model(s, 256, 128) for s, _ in batch]
+    items = [(s, len(p)) for s, p in batch]
+    for max_segments, max_units in sc.planner_trip_limits(models):
+        step("planner trips, limits", max_segments, max_units)
+        b = run(items, 256, 128, max_segments=max_segments, max_units=max_units, trace=True)
+        inside = same_as_model(b, models, (max_segments, max_units))
+        assert inside == (4 if sc.batch_words(models, max_segments, max_units) == sc.batch_words(models) else 3)
+        for i, (s, p) in enumerate(batch):
+            assert (int(b.status[i]), int(b.out_len[i])) == (rc.OK, len(p)) and b.window(i) == p, i
+
+
 BODIES = {f.__name__[5:]: f for f in (body_fixtures, body_fixtures_fall_back, body_own_compressor, body_hand_streams, body_mixed_batch,
-                                      body_flipped_bytes, body_limits)}
+                                      body_flipped_bytes, body_limits, body_fragment_built, body_model_batch, body_stream_ends,
+                                      body_planner_trips)}
 
 
 def in_child(name, *args):
@@ -242,3 +323,30 @@ def test_flipped_bytes_get_the_serial_verdict():
 
 def test_items_beyond_the_limits_fall_back_and_the_others_complete():
     in_child("limits")
+
+
+def test_fragment_built_streams_never_fall_back():
+    """Streams of elements no greedy compressor writes, fragment-built by construction: every flavour, units of the fragment and
+    of twice the fragment, padded headers: exactly [n, 0, 0, 0], the plaintext, and the model's cuts and nodes."""
+    in_child("fragment_built")
+
+
+@pytest.mark.parametrize("k", range(len(sc.CONFIGS)))
+def test_any_valid_stream_gets_the_models_words_cuts_and_nodes(k):
+    """About a hundred valid items in one call -- fragment-built at units that fit and that do not, raw-only elements, the hand
+    streams, the stream ends, the fixtures (first call): the result words are the model's sums; every cut and every node of
+    every split-class item is the model's; status, length and bytes are decode_raw's and the serial call's.  The model's own
+    coverage conditions (raw_split_cases.assert_covers) hold for each call."""
+    in_child("model_batch", k)
+
+
+def test_stream_ends_sized_byte_by_byte():
+    """Every element kind as the last element, its tag 1-7 bytes in front of src_len: valid, cut short by one byte, and with a
+    length field only its fifth byte makes too long."""
+    in_child("stream_ends")
+
+
+def test_more_items_than_one_trip_of_the_planner():
+    """1,032 items, split-class ones at 3, 1023, 1024 and 1030; with room for everything and with max_units / max_segments
+    ending just in front of and just behind item 1030."""
+    in_child("planner_trips")

@@ -68,6 +68,8 @@ def decode_raw(buf):
             ln = (tag >> 2) + 1
             if ln > 60:
                 extra = ln - 60
+                if i + extra > len(buf):
+                    raise ValueError("length field runs past the end of the stream")
                 ln = int.from_bytes(buf[i:i + extra], "little") + 1
                 i += extra
             if i + ln > len(buf):
@@ -75,6 +77,8 @@ def decode_raw(buf):
             out += buf[i:i + ln]
             i += ln
             continue
+        if i + (1, 2, 4)[kind - 1] > len(buf):
+            raise ValueError("copy runs past the end of the stream")
         if kind == 1:
             ln, off = ((tag >> 2) & 7) + 4, ((tag >> 5) << 8) | buf[i]
             i += 1
