@@ -255,6 +255,29 @@ SNAPPY_HIP_API int snappy_hip_decompress_blocks_batch(const struct snappy_hip_de
                                        void *stream);
 
 /*
+ * K2 with a whole workgroup on every block (csrc/snappy_k2_wide.hpp): for launches of a few blocks -- small files -- where
+ * snappy_hip_decompress_blocks leaves most of the device idle behind one wavefront per block.  Opt-in; same arguments, same
+ * answers: d_status[b] is exactly what snappy_hip_decompress_blocks writes for these arguments, where it is
+ * SNAPPY_HIP_BLOCK_OK the block's output bytes are too, and nothing outside d_out[0, total_len) is written whatever the
+ * stream holds.  waves_per_block wavefronts (0 = 16; else 2, 4, 8 or 16) find a block's elements in shares, prove the chain
+ * with K2's own element tests and resolve the copies in LDS.  A block takes that path only within the limits -- a block_size of
+ * at most SNAPPY_HIP_WIDE_MAX_BLOCK, a size word and payload inside the stream, at most SNAPPY_HIP_WIDE_MAX_CSZ
+ * compressed bytes (every compressor-made block of at most 32 KiB) -- and every other block, and every block the wide path
+ * does not prove, is decoded by K2's serial decoder inside the same launch: every SNAPPY_HIP_BLOCK_INVALID is its verdict.
+ * A block_size above SNAPPY_HIP_WIDE_MAX_BLOCK is no error: every block goes serial.
+ * d_result (4 u32, always written by an accepted call): [0] blocks the wide path decoded, [1] blocks sent to the serial
+ * decoder by the limits, [2] blocks the wide path did not prove, [3] 0.
+ * Only enqueues (the memsets of d_result and d_status, the work counter, one kernel on min(blocks, compute units) workgroups;
+ * SNAPPY_HIP_K2_WAVES caps that number of workgroups).  total_len == 0 launches nothing and writes d_result = 0.
+ * SNAPPY_HIP_ERR_ARG: a null d_result, null pointers with blocks present, a bad block_size or waves_per_block.
+ */
+#define SNAPPY_HIP_WIDE_MAX_BLOCK 32768u
+#define SNAPPY_HIP_WIDE_MAX_CSZ   38400u   /* >= 32 + 32768 + 32768 / 6 */
+SNAPPY_HIP_API int snappy_hip_decompress_blocks_wide(const uint8_t *d_stream, uint64_t stream_len, const uint64_t *d_block_offsets,
+                                      uint64_t total_len, uint32_t block_size, uint8_t *d_out, uint32_t *d_status,
+                                      uint32_t waves_per_block, uint32_t *d_result, void *stream);
+
+/*
  * Byte ranges of framed containers, decoded without the rest of them.  Range i asks for uncompressed bytes
  * [offset, offset + length) of container d_descs[stream] and gets them at dst.  Only the blocks a range touches are decoded:
  * a block wholly inside the range in place in dst, the first and last block of the range -- when only part of them is
@@ -625,6 +648,18 @@ SNAPPY_HIP_API int snappy_hip_raw_compress_batch(const snappy_hip_raw_item *d_it
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_range_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                           uint64_t offset, uint64_t length, struct program_runtime *runtime);
+
+/*
+ * The framed stream in input (the whole file: input->buffer at its first byte, input->length = file size) decoded to output
+ * through snappy_hip_decompress_blocks_wide: for small files.  Parses the header and walks the whole u32 size chain on the
+ * host (it must end exactly where the file does), one copy in, one wide launch on the current device with waves_per_block
+ * (0, 2, 4, 8 or 16), one copy out.  output as in snappy_decompress_range_gpu: realloc'd to the header's length, or used as is
+ * when output->max is finite (SNAPPY_BUFFER_TOO_SMALL if it does not fit); output->length = that length on success.  The same
+ * statuses as snappy_decompress_gpu for the same file; SNAPPY_INVALID_INPUT also for a bad waves_per_block.  No sharding.
+ * Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_wide_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                         uint32_t waves_per_block, struct program_runtime *runtime);
 
 /*
  * The framed stream in input with bytes [offset, offset + patch->length) of its plaintext replaced by patch->buffer, written

@@ -822,6 +822,60 @@ snappy_status decompress_range_gpu_body(struct host_buffer_context* input, struc
     return SNAPPY_OK;
 }
 
+// A whole framed file through the wide decoder (snappy_decompress_wide_gpu): the header and the whole size chain on the host,
+// the whole stream to the device, one snappy_hip_decompress_blocks_wide, the plaintext back.
+snappy_status decompress_wide_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t waves_per_block,
+                                       struct program_runtime* runtime)
+{
+    if (!input || !output || !runtime || !input->buffer) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    if (waves_per_block != 0 && waves_per_block != 2 && waves_per_block != 4 && waves_per_block != 8 && waves_per_block != 16)
+        return say(dropin_plan::refuse("waves_per_block %u is not 0, 2, 4, 8 or 16", waves_per_block));
+    const uint8_t* const buf = input->buffer;
+    const uint64_t in_total = input->length;
+    const dropin_plan::Container c = dropin_plan::open_container(buf, in_total);
+    const uint64_t nb = c.nb;
+    std::vector<uint64_t> off;
+    if (const dropin_plan::Verdict v = dropin_plan::walk_to(buf, in_total, c, nb, true, off)) return say(v);
+    const uint64_t total = c.total;
+    if (snappy_status st = claim_output(output, total)) return st;
+    place(output, 0);
+    if (total == 0) return call.done_on_host();
+    if (snappy_status st = call.need_device()) return st;
+
+    uint8_t *d_stream = nullptr, *d_out = nullptr;
+    uint64_t* d_boff = nullptr;
+    uint32_t *d_status = nullptr, *d_result = nullptr;
+    if (snappy_status st = call.buffers({{&d_stream, in_total}, {&d_boff, nb * sizeof(uint64_t)}, {&d_status, nb * sizeof(uint32_t)},
+                                         {&d_result, 4 * sizeof(uint32_t)}, {&d_out, total}}))
+        return st;
+    if (snappy_status st = call.upload({{d_stream, buf, in_total}, {d_boff, off.data(), nb * sizeof(uint64_t)}})) return st;
+    if (snappy_status st = call.launch("wide decode", [&] {
+            return snappy_hip_decompress_blocks_wide(d_stream, in_total, d_boff, total, c.bs, d_out, d_status, waves_per_block, d_result, nullptr);
+        }))
+        return st;
+    std::vector<uint32_t> status(nb, 0xffffffffu);
+    uint64_t bad = 0, first_bad = 0;
+    if (snappy_status st = call.copy_out([&]() -> int {
+            if (int rc = call.download({{status.data(), d_status, nb * sizeof(uint32_t)}})) return rc;
+            for (uint64_t b = nb; b-- > 0;)
+                if (status[b] != SNAPPY_HIP_BLOCK_OK) {
+                    ++bad;
+                    first_bad = b;
+                }
+            return bad ? 0 : call.download({{output->buffer, d_out, total}});
+        }))
+        return st;
+    if (snappy_status st = call.free_buffers()) return st;
+    if (bad) {
+        fprintf(stderr, "snappy_hip: %lu of %lu blocks do not decode, the first is block %lu\n", (unsigned long)bad, (unsigned long)nb,
+                (unsigned long)first_bad);
+        return SNAPPY_INVALID_INPUT;
+    }
+    place(output, total);
+    return SNAPPY_OK;
+}
+
 // One overwrite of a framed file (snappy_update_range_gpu): the header and the whole size chain on the host, the whole stream
 // to the device, one write through snappy_hip_update_ranges, the new stream back.  `output` is left alone until it succeeds.
 snappy_status update_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* patch, uint64_t offset,
@@ -1189,6 +1243,12 @@ snappy_status snappy_decompress_range_gpu(struct host_buffer_context* input, str
                                           uint64_t length, struct program_runtime* runtime)
 {
     return entry_guard([&] { return decompress_range_gpu_body(input, output, offset, length, runtime); });
+}
+
+snappy_status snappy_decompress_wide_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t waves_per_block,
+                                         struct program_runtime* runtime)
+{
+    return entry_guard([&] { return decompress_wide_gpu_body(input, output, waves_per_block, runtime); });
 }
 
 snappy_status snappy_update_range_gpu(struct host_buffer_context* input, struct host_buffer_context* patch, uint64_t offset,

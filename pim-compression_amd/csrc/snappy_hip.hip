@@ -32,6 +32,7 @@
 #include "snappy_raw_split.hpp"
 #include "snappy_resize.hpp"
 #include "snappy_check.hpp"
+#include "snappy_k2_wide.hpp"
 
 namespace {
 
@@ -842,6 +843,37 @@ int snappy_hip_decompress_blocks_batch(const struct snappy_hip_decompress_item* 
             if (int rc = launch_decompress(w, block_size, stream)) return rc;
     }
     return SNAPPY_HIP_OK;
+}
+
+// ---- one block on a whole workgroup (snappy_k2_wide.hpp) ----
+static_assert(SNAPPY_HIP_WIDE_MAX_BLOCK == snappy_hip::kWideMaxBlock && SNAPPY_HIP_WIDE_MAX_CSZ == snappy_hip::kWideMaxCsz, "the wide path's limits");
+static_assert(SNAPPY_HIP_WIDE_MAX_CSZ >= 32u + 32768u + 32768u / 6u, "every compressor-made block of at most 32 KiB is within the limits");
+
+int snappy_hip_decompress_blocks_wide(const uint8_t* d_stream, uint64_t stream_len, const uint64_t* d_block_offsets, uint64_t total_len,
+                                      uint32_t block_size, uint8_t* d_out, uint32_t* d_status, uint32_t waves_per_block, uint32_t* d_result,
+                                      void* stream)
+{
+    if (waves_per_block == 0) waves_per_block = snappy_hip::kWideMaxWaves;
+    if (waves_per_block != 2 && waves_per_block != 4 && waves_per_block != 8 && waves_per_block != 16)
+        return fail(SNAPPY_HIP_ERR_ARG, "waves_per_block must be 0, 2, 4, 8 or 16");
+    if (!d_result) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (total_len)
+        if (int rc = check_stream(d_stream, d_block_offsets, total_len, block_size, d_out, d_status)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_result, 0, 4 * sizeof(uint32_t), st));
+    if (total_len == 0) return SNAPPY_HIP_OK;
+    const uint32_t nb = (uint32_t)snappy_hip_num_blocks(total_len, block_size);
+    // every block's status starts as "not decoded", as K2's launch has it
+    HIP_TRY(hipMemsetAsync(d_status, 0xff, (size_t)nb * sizeof(uint32_t), st));
+    return launch_counted(st, [&](uint32_t* counter) {
+        // one workgroup per CU (its LDS is most of a CU's); SNAPPY_HIP_K2_WAVES caps the grid, the unit being workgroups here
+        const launch_shape::DeviceShape shape = device_shape();
+        const uint32_t cap = (uint32_t)std::max(1, env_int("SNAPPY_HIP_K2_WAVES", (int)shape.cus));
+        const uint32_t grid = std::min(std::min(nb, shape.cus), cap);
+        hipLaunchKernelGGL(snappy_hip::k2_wide_kernel, dim3(grid), dim3(64 * waves_per_block), 0, st, d_stream, stream_len, d_block_offsets, total_len,
+                           block_size, d_out, d_status, nb, d_result, counter);
+        return 0;
+    });
 }
 
 // ---- byte ranges (snappy_ranges.hpp) ----

@@ -5,7 +5,7 @@
  * snappy_decompress_dpu (dpu_snappy.c:169-172, :189-192).  Without -d the host CPU codec runs,
  * as in the reference.  -d never falls back to the CPU.
  *
- *   dpu_snappy [-d] [-c] [-R] [-S [<unit_len>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
  *   dpu_snappy [-d] [-R] -T -i <input_file>
  */
 #include <getopt.h>
@@ -23,12 +23,13 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "**DEBUG BUILD**\n");
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
-	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] [-R] -T -i <input_file>\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
 	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S\n");
+	fprintf(stderr, "W: with -d, decompressing a block-framed file: put a workgroup of <waves> wavefronts (2, 4, 8 or 16, default 16) on every block instead of one wavefront; for small files\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
 	fprintf(stderr, "r: decompress only <length> bytes from uncompressed byte <offset> of the input\n");
@@ -114,7 +115,9 @@ int main(int argc, char **argv)
 	int use_check = 0;
 	int use_split = 0;
 	unsigned long split_unit = 0;
-	while ((opt = getopt(argc, argv, "dcRTS::b:g:i:o:r:w:t:a:")) != -1) {
+	int use_wide = 0;
+	unsigned long wide_waves = 0;
+	while ((opt = getopt(argc, argv, "dcRTS::W::b:g:i:o:r:w:t:a:")) != -1) {
 		switch (opt) {
 		case 'S': {                  /* -S, -S<unit_len> or -S <unit_len> */
 			const char *arg = optarg;
@@ -129,6 +132,21 @@ int main(int argc, char **argv)
 				}
 			}
 			use_split = 1;
+			break;
+		}
+		case 'W': {                  /* -W, -W<waves> or -W <waves> */
+			const char *arg = optarg;
+			if (!arg && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
+				arg = argv[optind++];
+			if (arg) {
+				char *rest = NULL;
+				wide_waves = strtoul(arg, &rest, 10);
+				if (rest == arg || *rest != '\0' || (wide_waves != 2 && wide_waves != 4 && wide_waves != 8 && wide_waves != 16)) {
+					fprintf(stderr, "-W wants <waves> per block: 2, 4, 8 or 16, got '%s'\n", arg);
+					return -2;
+				}
+			}
+			use_wide = 1;
 			break;
 		}
 		case 'T': use_check = 1; break;
@@ -202,6 +220,10 @@ int main(int argc, char **argv)
 		return -2;
 	}
 	const int use_resize = use_keep || tail_path;
+	if (use_wide && (compress || raw || use_range || use_write || use_resize || use_check)) {
+		fprintf(stderr, "-W decodes a whole block-framed file: it does not go with -c, -R, -r, -w, -t, -a or -T\n");
+		return -2;
+	}
 	if (use_resize && (compress || use_range || use_write || raw)) {
 		fprintf(stderr, "-t and -a resize a compressed file: they do not go with -c, -r, -w or -R\n");
 		return -2;
@@ -376,6 +398,12 @@ int main(int argc, char **argv)
 			gettimeofday(&t1, NULL);
 			rt.run = get_runtime(&t0, &t1);
 		}
+	} else if (use_gpu && use_wide) {
+		/* a workgroup per block; the library reads the header itself and allocates the output (host mode ignores -W) */
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		st = snappy_decompress_wide_gpu(&input, &output, (uint32_t)wide_waves, &rt);
 	} else {
 		if (setup_decompression(&input, &output, &rt))
 			return -1;

@@ -98,6 +98,11 @@ def lib():
         L.snappy_hip_verify_index.argtypes = [vp, u32, vp]
         L.snappy_hip_decompress_blocks.restype = ctypes.c_int
         L.snappy_hip_decompress_blocks.argtypes = [vp, u64, vp, u64, u32, vp, vp, vp]
+        L.snappy_hip_decompress_blocks_wide.restype = ctypes.c_int
+        L.snappy_hip_decompress_blocks_wide.argtypes = [vp, u64, vp, u64, u32, vp, vp, u32, vp, vp]
+        L.snappy_decompress_wide_gpu.restype = ctypes.c_int
+        L.snappy_decompress_wide_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                                 ctypes.POINTER(ProgramRuntime)]
         L.snappy_hip_decompress_ranges_scratch_bytes.restype = u64
         L.snappy_hip_decompress_ranges_scratch_bytes.argtypes = [u32, u32]
         L.snappy_hip_decompress_ranges.restype = ctypes.c_int
@@ -323,6 +328,21 @@ def decompress_blocks(d_stream, stream_len, d_block_offsets, total_len, block_si
     _check(lib().snappy_hip_decompress_blocks(d_stream.data_ptr(), stream_len, d_block_offsets.data_ptr(), total_len,
                                               block_size, d_out.data_ptr(), d_status.data_ptr(), _stream_handle(torch)),
            "snappy_hip_decompress_blocks")
+
+
+WIDE_MAX_BLOCK, WIDE_MAX_CSZ = 32768, 38400      # SNAPPY_HIP_WIDE_MAX_BLOCK, SNAPPY_HIP_WIDE_MAX_CSZ
+
+
+def decompress_blocks_wide(d_stream, stream_len, d_block_offsets, total_len, block_size, d_out, d_status, d_result, waves_per_block=0):
+    """snappy_hip_decompress_blocks_wide: K2's arguments and answers, a workgroup of waves_per_block wavefronts (0 = 16) on every
+    block.  d_result: 4 int32 on the device (blocks decoded wide, sent to the serial decoder by the limits, not proven, 0)."""
+    import torch
+    _check(lib().snappy_hip_decompress_blocks_wide(d_stream.data_ptr() if d_stream is not None else None, stream_len,
+                                                   d_block_offsets.data_ptr() if d_block_offsets is not None else None, total_len, block_size,
+                                                   d_out.data_ptr() if d_out is not None else None,
+                                                   d_status.data_ptr() if d_status is not None else None, waves_per_block,
+                                                   d_result.data_ptr() if d_result is not None else None, _stream_handle(torch)),
+           "snappy_hip_decompress_blocks_wide")
 
 
 class _DecompressItem(ctypes.Structure):        # struct snappy_hip_decompress_item
@@ -665,6 +685,24 @@ def decompress_host(stream, out_len_override=None):
     plain = ctypes.string_at(out.buffer, total) if st == SNAPPY_OK else b""
     libc().free(buf)
     return st, plain, rt.as_dict()
+
+
+def decompress_host_wide(stream, waves_per_block=0, out_capacity=None):
+    """snappy_decompress_wide_gpu on a whole framed file held in host memory -> (status, bytes, runtime dict), as decompress_host.
+    out_capacity: hand over a caller-owned output buffer of that many bytes (finite `max`) instead of letting the callee allocate."""
+    a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
+    inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
+    if out_capacity is None:
+        out = HostBufferContext(b"<memory>", None, None, 0, (1 << 64) - 1)
+    else:
+        buf = libc().malloc(max(1, out_capacity))
+        out = HostBufferContext(b"<memory>", buf, buf, 0, out_capacity)
+    rt = ProgramRuntime()
+    st = lib().snappy_decompress_wide_gpu(ctypes.byref(inp), ctypes.byref(out), waves_per_block, ctypes.byref(rt))
+    data = ctypes.string_at(out.buffer, out.length) if st == SNAPPY_OK else b""
+    if out.buffer:
+        libc().free(out.buffer)
+    return st, data, rt.as_dict()
 
 
 def decompress_range_host(stream, offset, length, out_capacity=None):
