@@ -3,7 +3,9 @@ device and to the oracle.  Every job of tests/k2_window_cases.py and of tests/k2
 total_len = block_size = that block's output length, a one-entry offset array -- into ONE arena filled with ranges_cases.GUARD,
 ranges_cases.GAP guard bytes between the windows; the same jobs go through snappy_hip_decompress_blocks_batch into a second
 arena.  Status and bytes must be K2's, the result words follow from K2's status and the limits alone
-(k2_wide_cases.expected_result), and every guard byte is still there.  The wide call's own output is never a yardstick.  These
+(k2_wide_cases.expected_result), and every guard byte is still there.  The wide call's own output is never a yardstick.  The
+generated blocks, trips and small containers of k2_wide_cases are held to its model as well (verdict, bytes, result words),
+each block at all four workgroup sizes.  These
 inputs are rejected by bounds checks; none is built to fault."""
 import hashlib
 import os
@@ -45,8 +47,8 @@ def _stream_arena(streams):
     return torch.from_numpy(host).cuda(), offs
 
 
-def _both_decoders(shb, jobs):
-    """every job through K2 (one batch call) and through the wide call (one call each, W by turns) ->
+def _both_decoders(shb, jobs, shift=0):
+    """every job through K2 (one batch call) and through the wide call (one call each, W by turns, `shift` turns on) ->
     (K2 statuses, K2 arena, wide statuses, wide arena, result words per job, destination offsets)"""
     import torch
     streams = sorted({j[1] for j in jobs}, key=len)
@@ -64,7 +66,7 @@ def _both_decoders(shb, jobs):
         so = soffs[index[stream]]
         batch.append((d_streams[so:], len(stream), d_offs[k:k + 1], out_len, d_k2[dst[k]:], d_k2_status[k:k + 1]))
         shb.decompress_blocks_wide(d_streams[so:], len(stream), d_offs[k:k + 1], out_len, out_len, d_wide[dst[k]:], d_wide_status[k:k + 1],
-                                   d_result[k], ALL_WAVES[k % 4])
+                                   d_result[k], ALL_WAVES[(k + shift) % 4])
     shb.decompress_blocks_batch(batch, 65535)
     torch.cuda.synchronize()
     assert int(d_wide_status[len(jobs)]) == 7 and (d_result[len(jobs)].cpu().numpy() == 7).all()      # nothing behind the arrays
@@ -72,7 +74,7 @@ def _both_decoders(shb, jobs):
             d_result.cpu().numpy()[:len(jobs)], dst)
 
 
-def _check(jobs, answers):
+def _check(jobs, answers, shift=0):
     k2_status, k2_arena, status, arena, results, dst = answers
     problems, accepted, wide_path, expected = [], 0, 0, []
     for k, job in enumerate(jobs):
@@ -90,7 +92,7 @@ def _check(jobs, answers):
         if p is None and [int(x) for x in results[k]] != want:
             p = "%s: result words %r, expected %r" % (name, [int(x) for x in results[k]], want)
         if p:
-            problems.append("W=%d %s" % (ALL_WAVES[k % 4], p))
+            problems.append("W=%d %s" % (ALL_WAVES[(k + shift) % 4], p))
         accepted += st == 0
         wide_path += int(results[k][0])
         expected.append((dst[k], out_len, "any"))                         # inside its window a rejected block may hold anything
@@ -123,6 +125,87 @@ def test_hand_built_blocks_aimed_at_the_wide_path(shb, monkeypatch):
             problems, accepted, wide_path = _check(turn, _both_decoders(shb, turn))
             assert not problems, (cap, problems[:10])
             assert 0 < wide_path < len(jobs)
+
+
+@pytest.fixture(scope="module")
+def generated():
+    """the generated blocks of k2_wide_cases as jobs, made once"""
+    return wc.block_jobs(wc.small_blocks() + wc.large_blocks())
+
+
+@pytest.mark.parametrize("shift", [0, 1, 2, 3])
+def test_generated_blocks_against_k2_the_oracle_and_the_model(shb, generated, shift):
+    """k2_wide_cases.small_blocks and large_blocks (tests/test_k2_wide_model.py holds them to their coverage conditions), every
+    block at all four workgroup sizes over the four turns: K2's and the oracle's status and bytes (_check), and the model's
+    verdict, bytes and result words.  The invalid ones are rejected by bounds checks; none is built to fault."""
+    answers = _both_decoders(shb, generated, shift)
+    problems, accepted, wide_path = _check(generated, answers, shift)
+    status, arena, results, dst = answers[2], answers[3], answers[4], answers[5]
+    valid = 0
+    for k, job in enumerate(generated):
+        waves = ALL_WAVES[(k + shift) % 4]
+        m = wc.job_model(job, waves)
+        valid += m.valid
+        if int(status[k]) != (0 if m.valid else 1):
+            problems.append("W=%d %s: status %d, the model says valid = %r" % (waves, job[0], int(status[k]), m.valid))
+        elif m.valid and arena[dst[k]:dst[k] + job[3]].tobytes() != m.out:
+            problems.append("W=%d %s: bytes differ from the model's" % (waves, job[0]))
+        elif [int(x) for x in results[k]] != m.words:
+            problems.append("W=%d %s: result words %r, the model's %r" % (waves, job[0], [int(x) for x in results[k]], m.words))
+    assert not problems, (len(problems), problems[:10])
+    assert accepted == valid and wide_path == valid - 1                   # (one valid block lies beyond the csz limit)
+
+
+def _whole(shb, stream, offs, total, bs, waves):
+    """one container through K2 and through the wide call, its output behind GAP guard bytes ->
+    (K2 statuses, K2 bytes, wide statuses, wide bytes, result words); every guard byte and every word behind the arrays tested"""
+    import torch
+    d_stream, _ = _stream_arena([stream])
+    d_offs = torch.from_numpy(np.array(offs, dtype=np.int64)).cuda()
+    d_k2_out = torch.full((total,), rcases.GUARD, dtype=torch.uint8, device="cuda")
+    d_k2_status = torch.full((len(offs),), 7, dtype=torch.int32, device="cuda")
+    shb.decompress_blocks(d_stream, len(stream), d_offs, total, bs, d_k2_out, d_k2_status)
+    d_out = torch.full((rcases.GAP + total + 64,), rcases.GUARD, dtype=torch.uint8, device="cuda")
+    d_status = torch.full((len(offs) + 1,), 7, dtype=torch.int32, device="cuda")
+    d_result = torch.full((5,), 7, dtype=torch.int32, device="cuda")
+    shb.decompress_blocks_wide(d_stream, len(stream), d_offs, total, bs, d_out[rcases.GAP:], d_status, d_result, waves)
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    assert (out[:rcases.GAP] == rcases.GUARD).all() and (out[rcases.GAP + total:] == rcases.GUARD).all(), waves
+    status, result = [int(x) for x in d_status.cpu().numpy()], [int(x) for x in d_result.cpu().numpy()]
+    assert status[len(offs)] == 7 and result[4] == 7, waves
+    return ([int(x) for x in d_k2_status.cpu().numpy()], d_k2_out.cpu().numpy().tobytes(), status[:len(offs)],
+            out[rcases.GAP:rcases.GAP + total].tobytes(), result[:4])
+
+
+def test_trips_one_workgroup_meets_every_block_of_a_container_in_turn(shb, monkeypatch):
+    """k2_wide_cases.trips as whole-container calls with SNAPPY_HIP_K2_WAVES=1, which caps the wide call's grid at ONE workgroup:
+    what a trip leaves in LDS meets the next block.  Statuses, bytes and the summed result words are the model's and K2's."""
+    monkeypatch.setenv("SNAPPY_HIP_K2_WAVES", "1")
+    for name, stream, offs, total, bs, blocks in wc.trips():
+        for waves in ALL_WAVES:
+            models = [wc.model(body, n, waves) for body, n in blocks]
+            k2_status, k2_out, status, out, result = _whole(shb, stream, offs, total, bs, waves)
+            assert status == k2_status == [0 if m.valid else 1 for m in models], (name, waves, status)
+            assert result == [sum(m.words[i] for m in models) for i in range(4)], (name, waves, result)
+            for b, m in enumerate(models):
+                if m.valid:
+                    assert out[b * bs:b * bs + m.out_len] == m.out == k2_out[b * bs:b * bs + m.out_len], (name, waves, b)
+
+
+@pytest.mark.parametrize("cap", [None, "1"])
+def test_small_block_sizes_every_alignment_of_a_window(shb, monkeypatch, cap):
+    """100 blocks of 17 bytes -- with step F's head, middle and tail every alignment of a window against out_len 17 -- and block
+    sizes 1, 15, 16, 31, 33 and 48, behind GAP guard bytes, at all four workgroup sizes: the plaintext, K2's bytes, [0] = the
+    block count"""
+    if cap:
+        monkeypatch.setenv("SNAPPY_HIP_K2_WAVES", cap)
+    for name, stream, plain, offs, total, bs in wc.small_containers():
+        for waves in ALL_WAVES:
+            k2_status, k2_out, status, out, result = _whole(shb, stream, offs, total, bs, waves)
+            assert status == k2_status == [0] * len(offs), (name, waves)
+            assert out == plain == k2_out, (name, waves)
+            assert result == [len(offs), 0, 0, 0], (name, waves)
 
 
 def _golden_plain_ok(name, out):
