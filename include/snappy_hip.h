@@ -518,7 +518,8 @@ SNAPPY_HIP_API int snappy_hip_check_blocks(const snappy_hip_stream_desc *d_descs
  * estimate, not a measurement of this kernel); the device is full only with thousands of items.  Decoding ONE large raw file
  * with that call is therefore slower than the host mode.  That is a property of that call, not of the format: streams are
  * built from independently compressed fragments, and snappy_hip_raw_decompress_split_batch (below) finds and proves them.
- * (Compression has no such limit: the fragments of one item compress in parallel.)
+ * (Compression has no such limit: the fragments of one item compress in parallel.)  CHECKING one large stream has no such
+ * limit either, and needs no fragments: snappy_hip_raw_check_split_batch (below) spreads any stream over the device.
  */
 typedef struct snappy_hip_raw_item {
 	const void *src;        /* device: the input of this item, any alignment            */
@@ -564,6 +565,7 @@ SNAPPY_HIP_API int snappy_hip_raw_decompress_batch(const snappy_hip_raw_item *d_
  * = the header's length whenever the header parses.  The payload of a long literal is skipped, not read.
  * count == 0 is OK and launches nothing.  The call only enqueues work on `stream`; it never synchronises, never calls the
  * allocator and needs no scratch.  SNAPPY_HIP_ERR_ARG (host side): null arrays with count > 0.
+ * One wavefront walks a whole stream: for one LARGE stream use snappy_hip_raw_check_split_batch (below).
  */
 SNAPPY_HIP_API int snappy_hip_raw_check_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint64_t *d_out_len, uint32_t *d_status,
                                void *stream);
@@ -604,6 +606,38 @@ SNAPPY_HIP_API int snappy_hip_raw_decompress_split_batch(const snappy_hip_raw_it
                                           uint32_t segment_bytes, uint64_t max_segments, uint64_t max_units,
                                           uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result, void *d_scratch,
                                           uint64_t scratch_bytes, void *stream);
+
+/*
+ * snappy_hip_raw_check_batch with every LARGE item checked by many wavefronts, WHATEVER ITS SHAPE.  For every item
+ * (d_status[i], d_out_len[i]) equals what snappy_hip_raw_check_batch gives the same item; dst and dst_capacity are ignored.
+ * How: a check needs no earlier output -- every test uses an element's own fields and its absolute output position.  The
+ * call cuts the compressed bytes into segments, walks the element chains of every segment in parallel and joins them along
+ * the item, as snappy_hip_raw_decompress_split_batch does (the join is the one serial step: a table lookup per segment);
+ * then every stretch of the true chain is walked again by a wavefront of its own with its output position known, and every
+ * element on it gets the serial checker's tests: predecode's, the length bound, and a copy's offset against its absolute
+ * position.  An item whose chain ends exactly at src_len with exactly the header's length and whose stretches all pass and
+ * link up is OK by the serial checker's own rules.  Every other large item is judged by the serial checker inside the same
+ * call, so a VALID large stream inside the limit is always proven by the parallel path, whatever built it, and only invalid
+ * ones cost the serial time (csrc/snappy_raw_check_split.hpp).  There is no unit length.
+ *   segment_bytes  compressed bytes per segment; 0 = the default, 16 KiB.  A multiple of 64, at least 128.
+ *   max_segments   what the scratch has room for: the segments (ceil((src_len - header) / segment_bytes)) of the large items
+ *                  are counted in item order; an item whose segments lie beyond the limit, and every large item behind it, is
+ *                  checked serially.  That is not an error.
+ * An item is LARGE when it has more than one segment.
+ * d_result, 4 words, always written by an accepted call: [0] large items the parallel path proved, [1] items that are not
+ * large, checked serially, [2] large items sent to the serial checker because they are beyond max_segments or were not
+ * proven, [3] 0.  Items settled by their header (a bad header, TOO_LARGE, a length of 0) are in none of them.
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_raw_check_split_scratch_bytes(...) bytes (0 for a bad
+ * segment_bytes), not shared with a launch that runs concurrently; contents need not be initialised.  It holds a u64 and a
+ * u32 per item (the segment prefix and the flags), 64 x 8 bytes of table per segment and a 16-byte node per segment.
+ * The call only enqueues work on `stream` (five kernels); it never synchronises and never calls the allocator; the verdicts
+ * stay on the device.  count == 0 is OK and writes d_result = 0.  SNAPPY_HIP_ERR_ARG (host side): a bad segment_bytes, a null
+ * d_result, null arrays with count > 0, a scratch that is misaligned or too small; a refused call enqueues nothing.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_raw_check_split_scratch_bytes(uint32_t count, uint32_t segment_bytes, uint64_t max_segments);
+SNAPPY_HIP_API int snappy_hip_raw_check_split_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t segment_bytes,
+                                     uint64_t max_segments, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result,
+                                     void *d_scratch, uint64_t scratch_bytes, void *stream);
 
 /*
  * Item i's src[0, src_len) is plaintext; its output is varint(src_len) followed by the elements K1 produces for each
@@ -745,10 +779,17 @@ SNAPPY_HIP_API snappy_status snappy_check_gpu(struct host_buffer_context *input,
  * The same for the raw Snappy stream in input: one item through snappy_hip_raw_check_batch on the current device (one
  * wavefront walks the whole stream).  *uncompressed_len (may be NULL) = the header's length, 0 when it cannot be read.
  * SNAPPY_INVALID_INPUT: a malformed header, a stream or length above SNAPPY_HIP_RAW_MAX_LEN, or elements that would not decode.
- * Fills every field of *runtime.
+ * Fills every field of *runtime.  For one large file snappy_check_raw_split_gpu (below) is the faster call.
  */
 SNAPPY_HIP_API snappy_status snappy_check_raw_gpu(struct host_buffer_context *input, uint64_t *uncompressed_len,
                                    struct program_runtime *runtime);
+
+/*
+ * snappy_check_raw_gpu through snappy_hip_raw_check_split_batch (1a): the same file, the same answers, the stream checked by
+ * many wavefronts at the default segment, with a limit sized from the file.
+ */
+SNAPPY_HIP_API snappy_status snappy_check_raw_split_gpu(struct host_buffer_context *input, uint64_t *uncompressed_len,
+                                         struct program_runtime *runtime);
 
 #ifdef __cplusplus
 }

@@ -1164,8 +1164,9 @@ snappy_status check_gpu_body(struct host_buffer_context* input, snappy_hip_check
     return SNAPPY_INVALID_INPUT;
 }
 
-// Is a raw Snappy file intact (snappy_check_raw_gpu)?  One item through snappy_hip_raw_check_batch.
-snappy_status check_raw_gpu_body(struct host_buffer_context* input, uint64_t* uncompressed_len, struct program_runtime* runtime)
+// Is a raw Snappy file intact (snappy_check_raw_gpu)?  One item through snappy_hip_raw_check_batch, or -- split, snappy_check_raw_split_gpu --
+// through snappy_hip_raw_check_split_batch at its default segment with a limit sized from the file.
+snappy_status check_raw_gpu_body(struct host_buffer_context* input, uint64_t* uncompressed_len, struct program_runtime* runtime, bool split = false)
 {
     if (!input || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
     PhasedCall call(runtime);
@@ -1182,13 +1183,20 @@ snappy_status check_raw_gpu_body(struct host_buffer_context* input, uint64_t* un
         return SNAPPY_INVALID_INPUT;
     }
     if (snappy_status st = call.need_device()) return st;
-    uint8_t* d_in = nullptr;
+    const uint64_t segments = in_len / 16384u + 1;                          // (the default segment_bytes)
+    const uint64_t scratch_bytes = split ? snappy_hip_raw_check_split_scratch_bytes(1, 0, segments) : 0;
+    uint8_t *d_in = nullptr, *d_scratch = nullptr;
     snappy_hip_raw_item* d_item = nullptr;
     RawVerdict* d_verdict = nullptr;
-    if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict}})) return st;
+    if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict}, {&d_scratch, scratch_bytes}}))
+        return st;
     const snappy_hip_raw_item item{d_in, in_len, nullptr, 0};
     if (snappy_status st = call.upload({{d_in, input->buffer, in_len}, {d_item, &item, sizeof item}})) return st;
-    if (snappy_status st = call.launch("raw check", [&] { return snappy_hip_raw_check_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr); }))
+    if (snappy_status st = call.launch("raw check", [&] {
+            return split ? snappy_hip_raw_check_split_batch(d_item, 1, 0, segments, &d_verdict->out_len, &d_verdict->status, d_verdict->result,
+                                                            d_scratch, scratch_bytes, nullptr)
+                         : snappy_hip_raw_check_batch(d_item, 1, &d_verdict->out_len, &d_verdict->status, nullptr);
+        }))
         return st;
     RawVerdict v{};
     v.status = 0xffffffffu;
@@ -1288,6 +1296,11 @@ snappy_status snappy_check_gpu(struct host_buffer_context* input, snappy_hip_che
 snappy_status snappy_check_raw_gpu(struct host_buffer_context* input, uint64_t* uncompressed_len, struct program_runtime* runtime)
 {
     return entry_guard([&] { return check_raw_gpu_body(input, uncompressed_len, runtime); });
+}
+
+snappy_status snappy_check_raw_split_gpu(struct host_buffer_context* input, uint64_t* uncompressed_len, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return check_raw_gpu_body(input, uncompressed_len, runtime, true); });
 }
 
 }  // extern "C"

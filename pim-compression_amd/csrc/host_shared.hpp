@@ -1,0 +1,59 @@
+// host_shared.hpp -- the host-side helpers that every source of libsnappy_hip.so uses, defined once in snappy_hip.hip: the last
+// error, the launch of a persistent kernel on a work counter of its own, and the grid of the persistent decode / check kernels.
+// The namespace is hidden: none of this is in the library's dynamic symbol table (tests/test_abi_symbols.py).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/snappy_hip.h"
+
+namespace snappy_hip_host __attribute__((visibility("hidden"))) {
+
+extern thread_local std::string g_last_error;      // what snappy_hip_last_error() returns
+
+int fail(int code, const std::string& what);       // sets the last error, returns code
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(SNAPPY_HIP_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+    } while (0)
+
+// a zeroed counter for one launch on `st`; call work_counter_launched() right after the launch
+struct WorkCounterRing;
+struct WorkCounter {
+    uint32_t* ptr = nullptr;
+    hipEvent_t done = nullptr;
+    WorkCounterRing* ring = nullptr;
+    uint32_t slot = 0;
+};
+int next_work_counter(WorkCounter* out, hipStream_t st);
+// records the launch's completion event on `st` and releases the slot for reuse behind that event
+int work_counter_launched(const WorkCounter& c, hipStream_t st);
+
+// One launch of a persistent kernel on a counter of its own: launch(counter) enqueues the kernel on `st` and returns 0, or
+// refuses with fail(...) before it launches anything (the counter is handed back, the refusal is what the caller hears).
+// A failure of the counter (taking it, or handing it back) is reported before the launch's own error.
+template <class Launch>
+int launch_counted(hipStream_t st, Launch launch)
+{
+    WorkCounter wc;
+    if (int rc = next_work_counter(&wc, st)) return rc;
+    if (int rc = launch(wc.ptr)) {
+        const std::string refusal = g_last_error;
+        (void)work_counter_launched(wc, st);
+        return fail(rc, refusal);
+    }
+    const hipError_t launched = hipGetLastError();
+    if (int rc = work_counter_launched(wc, st)) return rc;
+    HIP_TRY(launched);
+    return 0;
+}
+
+// wavefronts of a persistent decode / check kernel whose work is counted on the device: K2's grid (SNAPPY_HIP_K2_WAVES)
+uint32_t range_grid_cap();
+
+}  // namespace snappy_hip_host

@@ -151,6 +151,41 @@ __device__ __forceinline__ uint64_t check_blocks_of(const StreamDesc& d)
     return nb;
 }
 
+// One item checked by ONE wavefront, verdict and length stored: a trip of raw_check_kernel and of the split check's serial step
+// (snappy_raw_check_split.hpp).  i is wave-uniform; every lane of the wavefront runs it.  A macro for SNAPPY_RAW_ITEM_VERDICT's
+// reason: raw_check_kernel's generated code stays what it was.
+#define SNAPPY_RAW_CHECK_ITEM(items, i, out_len, status, lane)                                                                    \
+    const uint8_t* src = load_global_ptr(&items[i].src);                                                                          \
+    const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));                                          \
+    /* the header, by raw_decompress_kernel's rule: at most 5 bytes, the fifth below 16, inside the stream */                     \
+    uint32_t length = 0, hdr = 0;                                                                                                 \
+    if (src)                                                                                                                      \
+        for (uint32_t k = 0; k < 5 && k < src_len; ++k) {                                                                         \
+            const uint32_t c = uni((uint32_t)src[k]);                                                                             \
+            if (k == 4 && c >= 16u) break;                                                                                        \
+            length |= (c & 0x7fu) << (7u * k);                                                                                    \
+            if (c < 0x80u) {                                                                                                      \
+                hdr = k + 1;                                                                                                      \
+                break;                                                                                                            \
+            }                                                                                                                     \
+        }                                                                                                                         \
+    uint32_t st;                                                                                                                  \
+    if (hdr == 0) {                                                                                                               \
+        st = kBlockInvalid;                                                                                                       \
+        length = 0;                                                                                                               \
+    } else if (src_len > kRawMaxLen || length > kRawMaxLen) {                                                                     \
+        st = kRawTooLarge;                                                                                                        \
+    } else if (length == 0) {                                                                                                     \
+        st = src_len == hdr ? kBlockOk : kBlockInvalid;          /* nothing may follow the header */                              \
+    } else {                                                                                                                      \
+        st = k2_check_block<true>(src, src_len, hdr, length);                                                                     \
+    }                                                                                                                             \
+    if (lane == 0) {                                                                                                              \
+        status[i] = st;                                                                                                           \
+        out_len[i] = length;                                                                                                      \
+    }
+
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(1024) void check_plan_kernel(const StreamDesc* __restrict__ descs, uint32_t count, uint32_t* __restrict__ results,
                                                           uint64_t* __restrict__ prefix)
 {
@@ -236,37 +271,10 @@ __global__ __launch_bounds__(64) void raw_check_kernel(const RawItem* __restrict
     for (;;) {
         const uint32_t i = draw_work(next_item, lane);
         if (i >= count) break;
-        const uint8_t* src = load_global_ptr(&items[i].src);
-        const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));
-        // the header, by raw_decompress_kernel's rule: at most 5 bytes, the fifth below 16, inside the stream
-        uint32_t length = 0, hdr = 0;
-        if (src)
-            for (uint32_t k = 0; k < 5 && k < src_len; ++k) {
-                const uint32_t c = uni((uint32_t)src[k]);
-                if (k == 4 && c >= 16u) break;
-                length |= (c & 0x7fu) << (7u * k);
-                if (c < 0x80u) {
-                    hdr = k + 1;
-                    break;
-                }
-            }
-        uint32_t st;
-        if (hdr == 0) {
-            st = kBlockInvalid;
-            length = 0;
-        } else if (src_len > kRawMaxLen || length > kRawMaxLen) {
-            st = kRawTooLarge;
-        } else if (length == 0) {
-            st = src_len == hdr ? kBlockOk : kBlockInvalid;          // nothing may follow the header
-        } else {
-            st = k2_check_block<true>(src, src_len, hdr, length);
-        }
-        if (lane == 0) {
-            status[i] = st;
-            out_len[i] = length;
-        }
+        SNAPPY_RAW_CHECK_ITEM(items, i, out_len, status, lane)
         __syncthreads();            // (the wavefront stays together from one draw to the next: see check_kernel)
     }
 }
+#endif
 
 }  // namespace snappy_hip

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/snappy_hip.h"
+#include "host_shared.hpp"
 #include "shard_devices.hpp"
 #include "launch_shape.hpp"
 #include "dropin_plan.hpp"
@@ -34,7 +35,7 @@
 #include "snappy_check.hpp"
 #include "snappy_k2_wide.hpp"
 
-namespace {
+namespace snappy_hip_host {   // (shared with the library's other sources: host_shared.hpp)
 
 thread_local std::string g_last_error;
 
@@ -44,12 +45,10 @@ int fail(int code, const std::string& what)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(SNAPPY_HIP_ERR_RUNTIME, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
+}  // namespace snappy_hip_host
+using namespace snappy_hip_host;
+
+namespace {
 
 double now_seconds()
 {
@@ -102,12 +101,14 @@ constexpr int kDefaultK1Stream = 1;     // SNAPPY_HIP_K1_STREAM: bit 0 = stream 
 constexpr uint32_t kWorkCounterSlots = 256;
 __device__ uint32_t g_work_counters[kWorkCounterSlots * 16];      // one counter per 64-byte line
 
-struct WorkCounterRing {
+}  // namespace
+struct snappy_hip_host::WorkCounterRing {
     std::mutex m;
     uint32_t turn = 0;
     hipEvent_t busy[kWorkCounterSlots] = {};
     bool taken[kWorkCounterSlots] = {};      // handed out, launch event not recorded yet
 };
+namespace {
 WorkCounterRing* work_counter_ring(int dev)
 {
     static WorkCounterRing* rings[64] = {};
@@ -117,14 +118,9 @@ WorkCounterRing* work_counter_ring(int dev)
     return rings[dev];
 }
 
-// a zeroed counter for one launch on `st`; call work_counter_launched() right after the launch
-struct WorkCounter {
-    uint32_t* ptr = nullptr;
-    hipEvent_t done = nullptr;
-    WorkCounterRing* ring = nullptr;
-    uint32_t slot = 0;
-};
-int next_work_counter(WorkCounter* out, hipStream_t st)
+}  // namespace
+
+int snappy_hip_host::next_work_counter(WorkCounter* out, hipStream_t st)
 {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -158,8 +154,7 @@ int next_work_counter(WorkCounter* out, hipStream_t st)
     }
     return 0;
 }
-// records the launch's completion event on `st` and releases the slot for reuse behind that event
-int work_counter_launched(const WorkCounter& c, hipStream_t st)
+int snappy_hip_host::work_counter_launched(const WorkCounter& c, hipStream_t st)
 {
     const hipError_t e = hipEventRecord(c.done, st);
     {
@@ -170,24 +165,7 @@ int work_counter_launched(const WorkCounter& c, hipStream_t st)
     return 0;
 }
 
-// One launch of a persistent kernel on a counter of its own: launch(counter) enqueues the kernel on `st` and returns 0, or
-// refuses with fail(...) before it launches anything (the counter is handed back, the refusal is what the caller hears).
-// A failure of the counter (taking it, or handing it back) is reported before the launch's own error.
-template <class Launch>
-int launch_counted(hipStream_t st, Launch launch)
-{
-    WorkCounter wc;
-    if (int rc = next_work_counter(&wc, st)) return rc;
-    if (int rc = launch(wc.ptr)) {
-        const std::string refusal = g_last_error;
-        (void)work_counter_launched(wc, st);
-        return fail(rc, refusal);
-    }
-    const hipError_t launched = hipGetLastError();
-    if (int rc = work_counter_launched(wc, st)) return rc;
-    HIP_TRY(launched);
-    return 0;
-}
+namespace {
 
 // Helper stream + fork/join events for launches that co-run two kernels, one set per (host thread, device).  The
 // events are timing-disabled; the helper stream is non-blocking, so the only ordering is the explicit fork (ev_begin)
@@ -877,12 +855,14 @@ int snappy_hip_decompress_blocks_wide(const uint8_t* d_stream, uint64_t stream_l
 }
 
 // ---- byte ranges (snappy_ranges.hpp) ----
-static uint32_t range_grid_cap()
+}  // extern "C"
+uint32_t snappy_hip_host::range_grid_cap()
 {
     const launch_shape::DeviceShape shape = device_shape();
     const int cap = std::max(1, env_int("SNAPPY_HIP_K2_WAVES", (int)shape.wave_slots()));
     return launch_shape::k2_launch_waves(shape, ~0ull, cap);
 }
+extern "C" {
 
 uint64_t snappy_hip_decompress_ranges_scratch_bytes(uint32_t max_block_size, uint32_t range_count)
 {

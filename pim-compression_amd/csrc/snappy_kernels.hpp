@@ -13,6 +13,10 @@
 //
 // Bit-exactness target: the reference HOST path, snappy/snappy_compress.c:284-413 and
 // snappy/snappy_decompress.c:218-289 (cited per function below).
+//
+// SNAPPY_HIP_NO_KERNELS: the library is built from more than one source.  Every kernel that is not a template is defined by
+// snappy_hip.hip alone; a further source (snappy_hip_raw_check_split.hip) defines this macro before it includes this header,
+// snappy_raw.hpp, snappy_check.hpp or snappy_raw_split.hpp and gets their __device__ pieces without a second copy of a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -1088,6 +1092,7 @@ __host__ __device__ inline uint32_t lds_table_stream_lds_bytes(uint32_t block_si
 // global-table kernel so that the LDS-table workgroups of the co-running kernel (33 KiB of LDS each) are placed first:
 // if the small LDS allocations of the global-table wavefronts land first they fragment the LDS and only two of the three
 // LDS-table workgroups per CU fit (block share 13-16 % instead of 22 %).
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64) void delay_kernel(uint32_t iters)
 {
 #ifndef SNAPPY_EMU
@@ -1096,6 +1101,7 @@ __global__ __launch_bounds__(64) void delay_kernel(uint32_t iters)
     (void)iters;
 #endif
 }
+#endif
 
 // One K1 launch can serve several containers (independent inputs with their own slot / size arrays): the persistent
 // wavefronts draw GLOBAL block numbers and map them to (container, block) here, so a batch has one tail instead of one per
@@ -1255,6 +1261,7 @@ namespace snappy_hip {
 
 // Single-workgroup exclusive scan (<= 131072 blocks per 4 GiB container at 32 KiB; any count
 // works, it loops).  Also writes the two header varints (snappy_compress.c:461-465).
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(1024) void scan_block_bytes_kernel(const uint32_t* __restrict__ block_bytes,
                                                                 uint32_t num_blocks, uint32_t total_len,
                                                                 uint32_t block_size, uint8_t* __restrict__ stream,
@@ -1302,6 +1309,7 @@ __global__ __launch_bounds__(256) void gather_slots_kernel(const uint8_t* __rest
         if (done + threadIdx.x < len) dst[done + threadIdx.x] = src[done + threadIdx.x];
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // size-chain index (device form of snappy_decompress.c:317-340); one wave per stream
@@ -1331,6 +1339,7 @@ constexpr uint32_t kIndexReaders = kIndexReaderWgs * kIndexWgWaves;
 constexpr uint32_t kIndexSuper = 8 * 4096;     // one read-ahead step of a wave: 8 loads x 64 lanes x 64 bytes apart
 constexpr uint32_t kIndexAheadSupers = 64;     // stay at most 2 MiB in front of the walker
 constexpr uint32_t kIndexRunning = 0x80000000u;
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64 * kIndexWgWaves) void index_streams_kernel(const StreamDesc* __restrict__ descs, uint32_t count,
                                                                            uint32_t group, const uint32_t* __restrict__ resolved = nullptr)
 {
@@ -1413,6 +1422,7 @@ __global__ __launch_bounds__(64 * kIndexWgWaves) void index_streams_kernel(const
     // keeps the loads alive: a condition the compiler cannot decide (a stream never has 2^32 - 1 blocks)
     if (sink == 0x9e3779b9u && d.num_blocks == 0xffffffffu) d.block_offsets[0] = sink;
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // The size chain in parallel segments (round 4).  The walk above is one chain of dependent loads, 162 ns per hop even with
@@ -1476,6 +1486,7 @@ __device__ __forceinline__ uint32_t chain_segments_of(uint64_t len, uint32_t hea
 }
 
 // grid: count x kChainSegments workgroups of one wavefront
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64) void chain_anchor_kernel(const StreamDesc* __restrict__ descs, uint32_t count, ChainWork w)
 {
     const uint32_t s = blockIdx.x / kChainSegments, k = blockIdx.x % kChainSegments;
@@ -1609,6 +1620,7 @@ __global__ __launch_bounds__(1024) void chain_finish_kernel(const StreamDesc* __
         w.resolved[s] = 1;
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // Verified side index.  The size chain is serial only when nothing is known about it.  When the caller already holds a
@@ -1620,6 +1632,7 @@ __global__ __launch_bounds__(1024) void chain_finish_kernel(const StreamDesc* __
 // the chain with index_streams_kernel.  descs[s].block_offsets holds num_blocks + 1 entries here.
 //   result[0] = SNAPPY_HIP_BLOCK_OK / _INVALID, result[1] = number of links that hold (num_blocks when the index is right)
 // ---------------------------------------------------------------------------
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64) void verify_index_begin_kernel(const StreamDesc* __restrict__ descs, uint32_t count)
 {
     const uint32_t s = blockIdx.x * 64 + threadIdx.x;
@@ -1660,6 +1673,7 @@ __global__ __launch_bounds__(256) void verify_index_kernel(const StreamDesc* __r
         if (good) atomicAdd(d.result + 1, good);
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // K2: decompress.  One wavefront per block.
@@ -2141,6 +2155,7 @@ struct K2Batch {
     uint32_t* status[kMaxBatch];
 };
 
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void decompress_blocks_kernel(const K2Batch w, uint32_t block_size,
                                                                                                     uint32_t* next_block)
 {
@@ -2173,6 +2188,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void decom
         __syncthreads();
     }
 }
+#endif
 
 
 }  // namespace snappy_hip

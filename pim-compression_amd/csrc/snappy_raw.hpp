@@ -88,6 +88,7 @@ struct RawItem {               // must match snappy_hip_raw_item (include/snappy
         out_len[i] = length;                                                                                                   \
     }
 
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64) void raw_decompress_kernel(const RawItem* __restrict__ items, uint32_t count, uint64_t* __restrict__ out_len,
                                                             uint32_t* __restrict__ status, uint32_t* next_item)
 {
@@ -102,6 +103,7 @@ __global__ __launch_bounds__(64) void raw_decompress_kernel(const RawItem* __res
         __syncthreads();
     }
 }
+#endif
 
 // ---- compress ----
 // words of the control line at the start of the scratch
@@ -124,6 +126,7 @@ __host__ __device__ inline RawLayout raw_layout(uint32_t count, uint32_t max_fra
     return l;
 }
 
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(1024) void raw_plan_kernel(const RawItem* __restrict__ items, uint32_t count, uint32_t block_size,
                                                         uint32_t max_fragments, uint64_t* __restrict__ out_len, uint32_t* __restrict__ status,
                                                         uint32_t* __restrict__ result, uint32_t* __restrict__ ctl, uint64_t* __restrict__ prefix)
@@ -162,6 +165,7 @@ __global__ __launch_bounds__(1024) void raw_plan_kernel(const RawItem* __restric
         result[1] = 0;
     }
 }
+#endif
 
 // kForm: the form of K1's parse the LDS-table kernel of the product runs at this block size (3 = stream, 2 = bulk); launched
 // with that kernel's dynamic LDS (lds_table_stream_lds_bytes / lds_table_kernel_lds_bytes)
@@ -193,6 +197,7 @@ __global__ __launch_bounds__(64) void raw_compress_fragments_kernel(const RawIte
 
 // One wavefront per item the plan left OK: the sizes of its fragments' payloads are scanned into their places behind the
 // header; an item that does not fit its dst is told the size it needs and keeps every byte of dst.
+#ifndef SNAPPY_HIP_NO_KERNELS
 __global__ __launch_bounds__(64) void raw_sizes_kernel(const RawItem* __restrict__ items, uint32_t count, const uint64_t* __restrict__ prefix,
                                                        const uint32_t* __restrict__ frag_bytes, uint64_t* __restrict__ place,
                                                        uint64_t* __restrict__ out_len, uint32_t* __restrict__ status, uint32_t* __restrict__ result)
@@ -240,5 +245,6 @@ __global__ __launch_bounds__(256) void raw_gather_kernel(const RawItem* __restri
         workgroup_copy(dst, src, frag_bytes[f] - 4u);
     }
 }
+#endif
 
 }  // namespace snappy_hip

@@ -113,9 +113,11 @@ __device__ __forceinline__ bool split_element_size(const uint8_t* src, uint64_t 
 // at or beyond stop_at (entry < stop_at <= stream_len <= kRawMaxLen): `landing` = that start, op_end = op0 + the output bytes of
 // the elements walked.  False when an element is invalid (as predecode_window<true> judges it against stream_len) or the
 // output would pass `length`.  kEmit: every element walked whose output position is a multiple of unit_len stores its
-// compressed position in cuts[position / unit_len].  Wave-uniform arguments; every lane of the wavefront calls it.  The
+// compressed position in cuts[position / unit_len].  kOffsets (the split check, snappy_raw_check_split.hpp): op0 is the entry's
+// ABSOLUTE output position in the item, and every copy walked is tested as k2_check_block tests it -- false for an offset of 0
+// or one larger than the copy's output position.  Wave-uniform arguments; every lane of the wavefront calls it.  The
 // cursors are K2's, relative to `entry` (see k2_check_block); a long literal is skipped, its payload never loaded.
-template <bool kEmit>
+template <bool kEmit, bool kOffsets = false>
 __device__ __forceinline__ bool split_walk(const uint8_t* stream, uint32_t stream_len, uint32_t entry, uint32_t stop_at, uint32_t op0,
                                            uint32_t length, uint32_t unit_len, uint32_t* cuts, uint32_t& landing, uint32_t& op_end)
 {
@@ -197,6 +199,14 @@ __device__ __forceinline__ bool split_walk(const uint8_t* stream, uint32_t strea
             ok = false;
             break;
         }
+        if constexpr (kOffsets) {
+            const uint32_t dstp = op + (incl - mylen);               // where this lane's element starts in the item's output
+            const unsigned long long COPY = E & __ballot(e_type != 0);
+            if (COPY & (__ballot(offv == 0) | __ballot(offv > dstp))) {
+                ok = false;
+                break;
+            }
+        }
         if constexpr (kEmit) {
             if (op + total > next_cut) {                             // a multiple of unit_len inside this window's output
                 const uint32_t dstp = op + (incl - mylen);           // where this lane's element starts in the item's output
@@ -229,6 +239,76 @@ __device__ __forceinline__ bool split_walk(const uint8_t* stream, uint32_t strea
     return ok;
 }
 
+// The body of the segment walk (step 2), shared with the split check (snappy_raw_check_split.hpp), whose step 2 it is too: a
+// macro for SNAPPY_RAW_ITEM_VERDICT's reason (snappy_raw.hpp).  The arguments are raw_split_walk_kernel's parameters.
+#define SNAPPY_SPLIT_WALK_SEGMENTS(items, count, segment_bytes, ctl, seg_prefix, flags, table, nodes, next_segment)               \
+    const uint32_t lane = threadIdx.x;                                                                                            \
+    const uint32_t segments = uni(ctl[kSplitCtlSegments]);                                                                        \
+    for (;;) {                                                                                                                    \
+        const uint32_t p = draw_work(next_segment, lane);                                                                         \
+        if (p >= segments) break;                                                                                                 \
+        const uint32_t i = prefix_owner<false>(seg_prefix, count, p);                                                             \
+        const uint8_t* src = load_global_ptr(&items[i].src);                                                                      \
+        const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));     /* (validated: <= kRawMaxLen) */ \
+        const uint32_t hdr = uni(flags[i]) >> 8;                                                                                  \
+        const uint64_t s = p - uld64(reinterpret_cast<const uint8_t*>(seg_prefix + i));                                           \
+        const uint64_t start = hdr + s * segment_bytes;                                                                           \
+        const uint64_t end = start + segment_bytes < src_len ? start + segment_bytes : src_len;                                   \
+        /* every lane a chain of its own: nothing below is wave-uniform, nothing in it talks to another lane */                   \
+        uint64_t pos = start + lane, out = 0;                                                                                     \
+        bool ok = true;                                                                                                           \
+        while (pos < end) {                                                                                                       \
+            uint32_t consumed, olen;                                                                                              \
+            if (!split_element_size(src, pos, src_len, consumed, olen)) {                                                         \
+                ok = false;                                                                                                       \
+                break;                                                                                                            \
+            }                                                                                                                     \
+            pos += consumed;                                                                                                      \
+            out += olen;                                                                                                          \
+        }                                                                                                                         \
+        if (out > kRawMaxLen) ok = false;                            /* (more than any header allows: no true chain) */           \
+        table[(uint64_t)p * kSplitZone + lane] = ok ? (pos | (out << 32)) : kSplitInvalid;                                        \
+        if (lane == 0) nodes[p] = make_uint4(kSplitNone, 0, 0, 0);   /* no step of the true chain starts here, until step 3 says so */\
+        __syncthreads();            /* (the wavefront stays together from one draw to the next: see check_kernel) */              \
+    }
+
+// The true chain of item i followed from the header's end (step 3), one node per step, shared with the split check.  Declares
+// src, src_len, length, hdr, first and `shaped` in the caller's scope.  i and flag (the item's flag word) are wave-uniform.
+#define SNAPPY_SPLIT_RESOLVE_CHAIN(items, i, flag, unit_len, segment_bytes, out_len, seg_prefix, table, nodes, lane)              \
+    const uint8_t* src = load_global_ptr(&items[i].src);                                                                          \
+    const uint32_t src_len = (uint32_t)uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));                                \
+    const uint32_t length = (uint32_t)uld64(reinterpret_cast<const uint8_t*>(out_len + i));                                       \
+    const uint32_t hdr = flag >> 8;                                                                                               \
+    const uint64_t first = uld64(reinterpret_cast<const uint8_t*>(seg_prefix + i));                                               \
+    uint32_t e = hdr, base = 0;                                                                                                   \
+    bool ok = true;                                                                                                               \
+    while (ok && e < src_len) {                                                                                                   \
+        const uint32_t s = (e - hdr) / segment_bytes;                                                                             \
+        const uint64_t zone = hdr + (uint64_t)s * segment_bytes;                                                                  \
+        const uint64_t zend = zone + segment_bytes;                                                                               \
+        const uint32_t end = zend < src_len ? (uint32_t)zend : src_len;                                                           \
+        uint32_t landing, out;                                                                                                    \
+        if (e - zone < kSplitZone) {                                                                                              \
+            const uint64_t t = uld64(reinterpret_cast<const uint8_t*>(table + (first + s) * kSplitZone + (e - zone)));            \
+            ok = t != kSplitInvalid;                                                                                              \
+            landing = (uint32_t)t;                                                                                                \
+            out = (uint32_t)(t >> 32);                                                                                            \
+        } else {                                                 /* behind a literal longer than the zone */                      \
+            uint32_t op_end;                                                                                                      \
+            ok = split_walk<false>(src, src_len, e, end, base, length, unit_len, nullptr, landing, op_end);                       \
+            out = op_end - base;                                                                                                  \
+        }                                                                                                                         \
+        if (!ok || out > length - base || landing <= e || landing > src_len) {                                                    \
+            ok = false;                                                                                                           \
+            break;                                                                                                                \
+        }                                                                                                                         \
+        if (lane == 0) nodes[first + s] = make_uint4(e, landing, base, 0);                                                        \
+        base += out;                                                                                                              \
+        e = landing;                                                                                                              \
+    }                                                                                                                             \
+    const bool shaped = ok && e == src_len && base == length;
+
+#ifndef SNAPPY_HIP_NO_KERNELS
 // ---- 1: plan ----
 __global__ __launch_bounds__(1024) void raw_split_plan_kernel(const RawItem* __restrict__ items, uint32_t count, uint32_t unit_len,
                                                               uint32_t segment_bytes, uint64_t max_segments, uint64_t max_units,
@@ -299,36 +379,7 @@ __global__ __launch_bounds__(64) void raw_split_walk_kernel(const RawItem* __res
                                                             const uint32_t* __restrict__ flags, uint64_t* __restrict__ table,
                                                             uint4* __restrict__ nodes, uint32_t* next_segment)
 {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t segments = uni(ctl[kSplitCtlSegments]);
-
-    for (;;) {
-        const uint32_t p = draw_work(next_segment, lane);
-        if (p >= segments) break;
-        const uint32_t i = prefix_owner<false>(seg_prefix, count, p);
-        const uint8_t* src = load_global_ptr(&items[i].src);
-        const uint64_t src_len = uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));     // (validated: <= kRawMaxLen)
-        const uint32_t hdr = uni(flags[i]) >> 8;
-        const uint64_t s = p - uld64(reinterpret_cast<const uint8_t*>(seg_prefix + i));
-        const uint64_t start = hdr + s * segment_bytes;
-        const uint64_t end = start + segment_bytes < src_len ? start + segment_bytes : src_len;
-        // every lane a chain of its own: nothing below is wave-uniform, nothing in it talks to another lane
-        uint64_t pos = start + lane, out = 0;
-        bool ok = true;
-        while (pos < end) {
-            uint32_t consumed, olen;
-            if (!split_element_size(src, pos, src_len, consumed, olen)) {
-                ok = false;
-                break;
-            }
-            pos += consumed;
-            out += olen;
-        }
-        if (out > kRawMaxLen) ok = false;                            // (more than any header allows: no true chain)
-        table[(uint64_t)p * kSplitZone + lane] = ok ? (pos | (out << 32)) : kSplitInvalid;
-        if (lane == 0) nodes[p] = make_uint4(kSplitNone, 0, 0, 0);   // no step of the true chain starts here, until step 3 says so
-        __syncthreads();            // (the wavefront stays together from one draw to the next: see check_kernel)
-    }
+    SNAPPY_SPLIT_WALK_SEGMENTS(items, count, segment_bytes, ctl, seg_prefix, flags, table, nodes, next_segment)
 }
 
 // ---- 3: resolve ----
@@ -342,38 +393,7 @@ __global__ __launch_bounds__(64) void raw_split_resolve_kernel(const RawItem* __
     for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
         const uint32_t flag = uld32(reinterpret_cast<const uint8_t*>(flags + i));
         if ((flag & (kSplitClassMask | kSplitFallback)) != kSplitSplit) continue;
-        const uint8_t* src = load_global_ptr(&items[i].src);
-        const uint32_t src_len = (uint32_t)uld64(reinterpret_cast<const uint8_t*>(&items[i].src_len));
-        const uint32_t length = (uint32_t)uld64(reinterpret_cast<const uint8_t*>(out_len + i));
-        const uint32_t hdr = flag >> 8;
-        const uint64_t first = uld64(reinterpret_cast<const uint8_t*>(seg_prefix + i));
-        uint32_t e = hdr, base = 0;
-        bool ok = true;
-        while (ok && e < src_len) {
-            const uint32_t s = (e - hdr) / segment_bytes;
-            const uint64_t zone = hdr + (uint64_t)s * segment_bytes;
-            const uint64_t zend = zone + segment_bytes;
-            const uint32_t end = zend < src_len ? (uint32_t)zend : src_len;
-            uint32_t landing, out;
-            if (e - zone < kSplitZone) {
-                const uint64_t t = uld64(reinterpret_cast<const uint8_t*>(table + (first + s) * kSplitZone + (e - zone)));
-                ok = t != kSplitInvalid;
-                landing = (uint32_t)t;
-                out = (uint32_t)(t >> 32);
-            } else {                                                 // behind a literal longer than the zone
-                uint32_t op_end;
-                ok = split_walk<false>(src, src_len, e, end, base, length, unit_len, nullptr, landing, op_end);
-                out = op_end - base;
-            }
-            if (!ok || out > length - base || landing <= e || landing > src_len) {
-                ok = false;
-                break;
-            }
-            if (lane == 0) nodes[first + s] = make_uint4(e, landing, base, 0);
-            base += out;
-            e = landing;
-        }
-        const bool shaped = ok && e == src_len && base == length;
+        SNAPPY_SPLIT_RESOLVE_CHAIN(items, i, flag, unit_len, segment_bytes, out_len, seg_prefix, table, nodes, lane)
         const uint64_t last_cut = uld64(reinterpret_cast<const uint8_t*>(unit_prefix + i)) + i + ((uint64_t)length + unit_len - 1u) / unit_len;
         if (lane == 0) {
             if (shaped) cuts[last_cut] = src_len;
@@ -481,5 +501,6 @@ __global__ __launch_bounds__(64) void raw_split_serial_kernel(const RawItem* __r
         __syncthreads();
     }
 }
+#endif
 
 }  // namespace snappy_hip

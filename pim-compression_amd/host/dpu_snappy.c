@@ -6,7 +6,7 @@
  * as in the reference.  -d never falls back to the CPU.
  *
  *   dpu_snappy [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
- *   dpu_snappy [-d] [-R] -T -i <input_file>
+ *   dpu_snappy [-d] [-R [-S]] -T -i <input_file>
  */
 #include <getopt.h>
 #include <limits.h>
@@ -24,11 +24,11 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
 	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
-	fprintf(stderr, "       %s [-d] [-R] -T -i <input_file>\n", exe);
+	fprintf(stderr, "       %s [-d] [-R [-S]] -T -i <input_file>\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
-	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S\n");
+	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S; with -d -R -T (no <unit_len>): check one large raw stream with many wavefronts, whatever built it\n");
 	fprintf(stderr, "W: with -d, decompressing a block-framed file: put a workgroup of <waves> wavefronts (2, 4, 8 or 16, default 16) on every block instead of one wavefront; for small files\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
@@ -115,6 +115,7 @@ int main(int argc, char **argv)
 	int use_check = 0;
 	int use_split = 0;
 	unsigned long split_unit = 0;
+	int split_has_unit = 0;
 	int use_wide = 0;
 	unsigned long wide_waves = 0;
 	while ((opt = getopt(argc, argv, "dcRTS::W::b:g:i:o:r:w:t:a:")) != -1) {
@@ -130,6 +131,7 @@ int main(int argc, char **argv)
 					fprintf(stderr, "-S wants <unit_len> in bytes, at least 256, got '%s'\n", arg);
 					return -2;
 				}
+				split_has_unit = 1;
 			}
 			use_split = 1;
 			break;
@@ -215,8 +217,12 @@ int main(int argc, char **argv)
 		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
 		return -2;
 	}
-	if (use_split && (!raw || compress || use_check)) {
-		fprintf(stderr, "-S splits the decoding of one raw Snappy stream: it goes with -R and not with -c or -T\n");
+	if (use_split && (!raw || compress)) {
+		fprintf(stderr, "-S splits the decoding or the check (-T) of one raw Snappy stream: it goes with -R and not with -c\n");
+		return -2;
+	}
+	if (use_split && use_check && split_has_unit) {
+		fprintf(stderr, "-S takes no <unit_len> with -T: a check has no units\n");
 		return -2;
 	}
 	const int use_resize = use_keep || tail_path;
@@ -262,7 +268,9 @@ int main(int argc, char **argv)
 		snappy_hip_check_report rep = { 0, 0, 0, 0 };
 		uint64_t raw_len = 0;
 		if (use_gpu) {
-			st = raw ? snappy_check_raw_gpu(&input, &raw_len, &rt) : snappy_check_gpu(&input, &rep, &rt);
+			st = !raw ? snappy_check_gpu(&input, &rep, &rt)
+			     : use_split ? snappy_check_raw_split_gpu(&input, &raw_len, &rt)
+			     : snappy_check_raw_gpu(&input, &raw_len, &rt);
 		} else {
 			gettimeofday(&t0, NULL);
 			st = raw ? snappy_check_raw_host(&input, &raw_len) : snappy_check_host(&input, &rep);

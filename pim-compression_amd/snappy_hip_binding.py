@@ -142,10 +142,16 @@ def lib():
         L.snappy_hip_check_blocks.argtypes = [vp, u32, vp, vp, vp, u64, vp]
         L.snappy_hip_raw_check_batch.restype = ctypes.c_int
         L.snappy_hip_raw_check_batch.argtypes = [vp, u32, vp, vp, vp]
+        L.snappy_hip_raw_check_split_scratch_bytes.restype = u64
+        L.snappy_hip_raw_check_split_scratch_bytes.argtypes = [u32, u32, u64]
+        L.snappy_hip_raw_check_split_batch.restype = ctypes.c_int
+        L.snappy_hip_raw_check_split_batch.argtypes = [vp, u32, u32, u64, vp, vp, vp, vp, u64, vp]
         L.snappy_check_gpu.restype = ctypes.c_int
         L.snappy_check_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(CheckReport), ctypes.POINTER(ProgramRuntime)]
         L.snappy_check_raw_gpu.restype = ctypes.c_int
         L.snappy_check_raw_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(u64), ctypes.POINTER(ProgramRuntime)]
+        L.snappy_check_raw_split_gpu.restype = ctypes.c_int
+        L.snappy_check_raw_split_gpu.argtypes = L.snappy_check_raw_gpu.argtypes
         L.snappy_update_range_gpu.restype = ctypes.c_int
         L.snappy_update_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64,
                                               ctypes.POINTER(HostBufferContext), ctypes.POINTER(ProgramRuntime)]
@@ -605,6 +611,26 @@ def raw_check_batch(d_items, count, d_out_len, d_status):
            "snappy_hip_raw_check_batch")
 
 
+def raw_check_split_scratch_bytes(count, segment_bytes, max_segments):
+    """Scratch of snappy_hip_raw_check_split_batch (0 for a bad segment_bytes)."""
+    return int(lib().snappy_hip_raw_check_split_scratch_bytes(count, segment_bytes, max_segments))
+
+
+def raw_check_split_batch(d_items, count, segment_bytes, max_segments, d_out_len, d_status, d_result, d_scratch=None):
+    """Enqueue snappy_hip_raw_check_split_batch on the current stream: raw_check_batch with every item of more than one segment
+    checked by many wavefronts, whatever built it.  segment_bytes: 0 = the default (16 KiB); max_segments: what the scratch is
+    sized for.  d_result: device int32 tensor of four (proven by the parallel path, not large, sent to the serial checker, 0).
+    d_scratch: 256-byte aligned device uint8 tensor (default: a fresh one).  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(raw_check_split_scratch_bytes(count, segment_bytes, max_segments), 256), dtype=torch.uint8, device=d_result.device)
+    _check(lib().snappy_hip_raw_check_split_batch(d_items.data_ptr() if count else None, count, segment_bytes, max_segments,
+                                                  d_out_len.data_ptr() if count else None, d_status.data_ptr() if count else None,
+                                                  d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(), _stream_handle(torch)),
+           "snappy_hip_raw_check_split_batch")
+    return d_scratch
+
+
 def check_resident(d_stream, stream_len=None):
     """Is the framed stream held in a CUDA uint8 tensor intact?  Indexes it (the size chain), then checks every block without
     decoding it -> (ok, bad_blocks, first_bad_block).  A broken header or chain: (False, 1, the number of blocks the walk
@@ -806,10 +832,16 @@ def raw_decompress_split_host(stream, unit_len=0, out_capacity=None):
     return _raw_host(lambda i, o, r: lib().snappy_decompress_raw_split_gpu(i, o, unit_len, r), stream, out_capacity)
 
 
-def check_raw_host(stream):
-    """snappy_check_raw_gpu on a whole raw Snappy stream held in host memory -> (status, uncompressed length, runtime dict)."""
+def check_raw_host(stream, split=False):
+    """snappy_check_raw_gpu -- split: snappy_check_raw_split_gpu -- on a whole raw Snappy stream held in host memory -> (status,
+    uncompressed length, runtime dict)."""
     a = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, dtype=np.uint8)
     inp = HostBufferContext(b"<memory>", a.ctypes.data, a.ctypes.data, len(stream), (1 << 64) - 1)
     length, rt = ctypes.c_uint64(0), ProgramRuntime()
-    st = lib().snappy_check_raw_gpu(ctypes.byref(inp), ctypes.byref(length), ctypes.byref(rt))
+    st = (lib().snappy_check_raw_split_gpu if split else lib().snappy_check_raw_gpu)(ctypes.byref(inp), ctypes.byref(length), ctypes.byref(rt))
     return st, int(length.value), rt.as_dict()
+
+
+def check_raw_split_host(stream):
+    """snappy_check_raw_split_gpu on a whole raw Snappy stream held in host memory -> (status, uncompressed length, runtime dict)."""
+    return check_raw_host(stream, split=True)

@@ -4,7 +4,7 @@
 ROOT=$PWD
 i=0
 for d in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -fvisibility=hidden -I$ROOT/include $d/snappy_hip.hip -o pim-compression_amd/libab_$i.so || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -fvisibility=hidden -I$ROOT/include $d/*.hip -o pim-compression_amd/libab_$i.so || exit 1
   i=$((i+1))
 done
 for rep in 1 2; do

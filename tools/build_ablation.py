@@ -10,9 +10,10 @@ OUT = os.path.join(ROOT, "pim-compression_amd", "libsnappy_hip_ablation.so")
 
 
 def build():
-    src = os.path.join(ROOT, "pim-compression_amd", "csrc", "snappy_hip.hip")
+    csrc = os.path.join(ROOT, "pim-compression_amd", "csrc")
+    srcs = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hip"))      # every source of the product library
     subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                           "-shared", "-DSNAPPY_ABLATION", src, "-o", OUT])
+                           "-shared", "-DSNAPPY_ABLATION"] + srcs + ["-o", OUT])
     return OUT
 
 

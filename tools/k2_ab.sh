@@ -1,11 +1,11 @@
 #!/bin/bash
 # A/B of library builds on ONE box (box-to-box differences reach 10 % for K2): tools/k2_ab.sh <csrc dir or flags> ...
-# An argument that is a directory is built from <dir>/snappy_hip.hip, anything else is passed to hipcc as flags for the
+# An argument that is a directory is built from every <dir>/*.hip, anything else is passed to hipcc as flags for the
 # working tree's csrc.  Each build is timed twice, alternating (tools/exp_variants.py, 2 GiB container).
 ROOT=$PWD
 i=0
 for v in "$@"; do
-  if [ -d "$v" ]; then srcf=$v/snappy_hip.hip; fl=""; else srcf=pim-compression_amd/csrc/snappy_hip.hip; fl=$v; fi
+  if [ -d "$v" ]; then srcf="$v/*.hip"; fl=""; else srcf="pim-compression_amd/csrc/*.hip"; fl=$v; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared $fl $srcf -o pim-compression_amd/libk2ab_$i.so || exit 1
   i=$((i+1))
 done

@@ -3,7 +3,7 @@
 # visits every 2^L-th element): two rocprofv3 --pmc passes per build, 2 GiB container.   bash tools/pmc_k2_walk_levels.sh 1 2 4
 ROOT=$PWD
 for L in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DSNAPPY_K2_WALK_LEVELS=$L pim-compression_amd/csrc/snappy_hip.hip -o pim-compression_amd/libk2walk_$L.so || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DSNAPPY_K2_WALK_LEVELS=$L pim-compression_amd/csrc/*.hip -o pim-compression_amd/libk2walk_$L.so || exit 1
   OUT=$ROOT/gpurun_out/pmc_k2_walk_$L
   mkdir -p $OUT
   i=0

@@ -7,8 +7,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "pim-compression_amd"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 LIB = os.path.join(ROOT, "pim-compression_amd", "libsnappy_hip_prof.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DSNAPPY_PROF",
-                       os.path.join(ROOT, "pim-compression_amd", "csrc", "snappy_hip.hip"), "-o", LIB])
+CSRC = os.path.join(ROOT, "pim-compression_amd", "csrc")
+subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DSNAPPY_PROF"] +
+                      sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip")) + ["-o", LIB])
 import numpy as np, torch
 import silesia_mix
 import snappy_hip_binding as shb
