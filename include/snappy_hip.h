@@ -669,6 +669,83 @@ SNAPPY_HIP_API int snappy_hip_raw_compress_batch(const snappy_hip_raw_item *d_it
                                   uint32_t max_fragments, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result,
                                   void *d_scratch, uint64_t scratch_bytes, void *stream);
 
+/* ---- 1a'. the Snappy framing format (.sz) and CRC-32C on the device ------ */
+
+/*
+ * The Snappy FRAMING format: what `snzip` writes by default (.sz) and Go's snappy.Writer / Reader, snappy-java's framed streams
+ * and python-snappy's stream classes speak; the one Snappy format that carries a checksum.  A stream is a chain of chunks: one
+ * type byte, a 3-byte little-endian length L, L bytes.
+ *   0xff        stream identifier: L = 6, "sNaPpY".  The first chunk; it may appear again anywhere (concatenated files).
+ *   0x00        compressed data: the masked CRC-32C (little-endian) of the UNCOMPRESSED bytes, then one raw Snappy stream of at
+ *               most 65,536 uncompressed bytes.
+ *   0x01        uncompressed data: the masked CRC, then L - 4 <= 65,536 plain bytes.
+ *   0x80..0xfe  padding / reserved skippable: skipped.        0x02..0x7f  reserved unskippable: the stream is refused.
+ * CRC-32C: the Castagnoli polynomial (reflected 0x82F63B78), init and final xor 0xFFFFFFFF; mask(c) = ((c >> 15) | (c << 17)) +
+ * 0xa282ead8.  Items are snappy_hip_raw_item (1a).
+ */
+typedef struct snappy_hip_crc_item {
+    const uint8_t *src;    /* device pointer, any alignment; may be NULL when src_len is 0 */
+    uint64_t src_len;      /* any length */
+} snappy_hip_crc_item;
+
+/*
+ * d_crc[i] = the (unmasked) CRC-32C of item i's src[0, src_len); 0 for an empty item (or a null src).  d_items and d_crc are
+ * device pointers to `count` entries.  One wavefront computes one item's CRC (persistent wavefronts draw items from a
+ * counter), so the device is full only with many items.  The call only enqueues work on `stream`.
+ */
+SNAPPY_HIP_API int snappy_hip_crc32c_batch(const snappy_hip_crc_item *d_items, uint32_t count, uint32_t *d_crc, void *stream);
+
+#define SNAPPY_HIP_SZ_CRC_MISMATCH 7u
+#define SNAPPY_HIP_SZ_UNSUPPORTED  8u
+#define SNAPPY_HIP_SZ_NO_VERIFY    1u   /* flags bit 0: do not compare the chunks' CRCs */
+
+/*
+ * Item i's src[0, src_len) is one .sz stream from any writer; its data chunks are decoded to dst back to back.  One wavefront
+ * per stream walks the chunk chain (serial per stream), then the data chunks of the whole batch are decoded in parallel, one
+ * wavefront per chunk, which also computes the CRC-32C of what it wrote and compares it with the stored one.
+ * Per item, always written:
+ *   SNAPPY_HIP_BLOCK_OK            dst[0, d_out_len[i]) is the plaintext, every CRC held (or flags had SNAPPY_HIP_SZ_NO_VERIFY).
+ *   SNAPPY_HIP_BLOCK_INVALID       the CHAIN is broken -- a null src, no identifier, a first chunk that is not the identifier, a
+ *                                  wrong identifier, a chunk running past src_len, a data chunk with L < 4 or of more than 65,536
+ *                                  uncompressed bytes, an unreadable length in a compressed chunk: d_out_len[i] = 0 and not one
+ *                                  byte of dst is written -- or a compressed CHUNK does not decode to the length it states: the
+ *                                  other chunks are decoded, d_bad_chunk[i] names the lowest-numbered bad one.
+ *   SNAPPY_HIP_SZ_UNSUPPORTED      the chain holds a reserved unskippable chunk (0x02..0x7f).  d_out_len[i] = 0, dst untouched.
+ *   SNAPPY_HIP_SZ_CRC_MISMATCH     chunk d_bad_chunk[i] (the lowest-numbered bad one) decodes but its CRC does not hold.
+ *   SNAPPY_HIP_RAW_DST_TOO_SMALL   the chain parses, d_out_len[i] = the total length exceeds dst_capacity (a null dst counts as
+ *                                  0): not one byte of dst is written.  A first call with capacities of 0 sizes the outputs.
+ *   SNAPPY_HIP_RAW_TOO_LARGE       src_len or the total length exceeds SNAPPY_HIP_RAW_MAX_LEN, or the item's chunks lie beyond
+ *                                  max_chunks of the call (the items in front of it complete).
+ * d_out_len[i] is the total uncompressed length whenever the chain parses.  d_bad_chunk[i]: the number, among the item's data
+ * chunks, of the first one that is bad, 0xffffffff if none (also for every fault of the chain).  Nothing outside
+ * [dst, dst + dst_capacity) is ever written.
+ * d_result[0] = the data chunks the whole batch needs (saturated at 2^32 - 1), d_result[1] = the number of items that are OK.
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_sz_decompress_scratch_bytes(count, max_chunks) bytes
+ * (a u64 per item, 32 bytes per chunk), not shared with a launch that runs concurrently; contents need not be initialised.
+ * The call only enqueues work on `stream`.  SNAPPY_HIP_ERR_ARG (host side): null arrays, an unknown flag, a bad scratch.
+ * There is no checksum-verifying check without an output buffer: the CRC is over the plaintext.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_sz_decompress_scratch_bytes(uint32_t count, uint32_t max_chunks);
+SNAPPY_HIP_API int snappy_hip_sz_decompress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t max_chunks, uint32_t flags,
+                                   uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_bad_chunk, uint32_t *d_result,
+                                   void *d_scratch, uint64_t scratch_bytes, void *stream);
+
+/*
+ * Item i's src[0, src_len) is plaintext; its output is the 10-byte stream identifier and one chunk per chunk_len (1..65535, K1's
+ * block limits) bytes of it, in order.  With R = varint32(n) + the elements K1 produces for the chunk's n bytes as one block
+ * (what snappy_hip_raw_compress_batch writes for those bytes alone), the chunk is of type 0x00 and carries R iff R is shorter
+ * than n bytes, else of type 0x01 and carries the plain bytes; either way behind the masked CRC-32C of the plain bytes.  The
+ * output is fully determined by the input and chunk_len; an empty item gives the identifier alone.
+ * snappy_hip_sz_compress_bound = 10 + 8 * chunks + src_len: the exact size when no chunk compresses, never exceeded.
+ * Statuses, d_result, d_scratch (snappy_hip_sz_compress_scratch_bytes(chunk_len, count, max_chunks)) and the host-side errors
+ * are those of snappy_hip_raw_compress_batch with chunks for fragments.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_sz_compress_bound(uint64_t src_len, uint32_t chunk_len);
+SNAPPY_HIP_API uint64_t snappy_hip_sz_compress_scratch_bytes(uint32_t chunk_len, uint32_t count, uint32_t max_chunks);
+SNAPPY_HIP_API int snappy_hip_sz_compress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks,
+                                 uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result, void *d_scratch,
+                                 uint64_t scratch_bytes, void *stream);
+
 /* ---- 1b. drop-in level: one byte range of a framed file ----------------- */
 
 /*
@@ -752,6 +829,28 @@ SNAPPY_HIP_API snappy_status snappy_decompress_raw_gpu(struct host_buffer_contex
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_raw_split_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                               uint32_t unit_len, struct program_runtime *runtime);
+
+/* ---- 1c'. drop-in level: one buffer of the Snappy framing format (.sz) ---- */
+
+/*
+ * input (plaintext, less than 4 GiB) as one .sz stream of chunk_len (1..65535) chunks, written to output (as in
+ * snappy_compress_gpu: realloc'd to the stream's size, or used as is when output->max is finite, SNAPPY_BUFFER_TOO_SMALL if it
+ * does not fit).  One item through snappy_hip_sz_compress_batch on the current device; no sharding.  The bytes are the ones
+ * `dpu_snappy -c -z` writes in host mode.  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_compress_sz_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                     uint32_t chunk_len, struct program_runtime *runtime);
+
+/*
+ * The .sz stream in input (the whole file, from any writer) decoded to output (realloc'd to the plaintext's length, or used as
+ * is when output->max is finite, SNAPPY_BUFFER_TOO_SMALL if it does not fit).  The chunk chain is walked on the host to size
+ * the call (a chain that does not parse is refused there), then one item goes through snappy_hip_sz_decompress_batch on the
+ * current device: its chunks decode in parallel and every chunk's CRC-32C is compared, unless flags has
+ * SNAPPY_HIP_SZ_NO_VERIFY.  SNAPPY_INVALID_INPUT: a broken chain, a reserved unskippable chunk, a chunk that does not decode or
+ * fails its CRC (named on stderr).  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_sz_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                       uint32_t flags, struct program_runtime *runtime);
 
 /* ---- 1d. drop-in level: is this file intact? ----------------------------- */
 

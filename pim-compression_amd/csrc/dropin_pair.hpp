@@ -1091,6 +1091,115 @@ snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, str
     return SNAPPY_OK;
 }
 
+// The Snappy framing format (.sz), one buffer each way: one item through the batch calls of snappy_sz.hpp.
+struct SzVerdict {             // what one item's call leaves on the device
+    uint64_t out_len;
+    uint32_t status;
+    uint32_t bad_chunk;
+    uint32_t result[2];
+};
+
+// The chunk chain of a .sz file by the rules of snappy_hip_sz_decompress_batch, to size the call: the number of data chunks and
+// the sum of their uncompressed lengths.  nullptr, or why the chain does not parse (the device would say the same).
+inline const char* sz_host_walk(const uint8_t* s, uint64_t len, uint64_t* chunks, uint64_t* total)
+{
+    uint64_t at = 0;
+    bool identified = false;
+    *chunks = *total = 0;
+    while (at < len) {
+        if (at + 4 > len) return "a chunk header runs past the end of the file";
+        const uint32_t type = s[at], L = s[at + 1] | (uint32_t)s[at + 2] << 8 | (uint32_t)s[at + 3] << 16;
+        if (at + 4 + L > len) return "a chunk runs past the end of the file";
+        if (type == 0xffu) {
+            if (L != 6 || memcmp(s + at + 4, "sNaPpY", 6) != 0) return "a wrong stream identifier";
+            identified = true;
+        } else if (!identified) {
+            return "the first chunk is not the stream identifier";
+        } else if (type <= 1u) {
+            if (L < 4) return "a data chunk without room for its checksum";
+            uint32_t n = L - 4;
+            if (type == 0 && !get_varint32(s + at + 8, L - 4, &n)) return "a compressed chunk without a readable length";
+            if (n > 65536u) return "a chunk of more than 65536 bytes";
+            *total += n;
+            ++*chunks;
+        } else if (type < 0x80u) {
+            return "a reserved unskippable chunk";
+        }
+        at += 4ull + L;
+    }
+    return identified ? nullptr : "no stream identifier";
+}
+
+// compress = true: plaintext -> .sz at chunk_len; false: .sz -> plaintext, every CRC compared unless flags says not to.
+snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t chunk_len, uint32_t flags,
+                          struct program_runtime* runtime)
+{
+    if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    const uint64_t in_len = input->length;
+    uint64_t capacity = 0, scratch_bytes = 0, chunks = 0;
+    if (compress) {
+        if (!block_size_ok(chunk_len)) return say(dropin_plan::bad_block_size(chunk_len, ""));
+        if (in_len >> 32) {
+            fprintf(stderr, "snappy_hip: one .sz item holds less than 4 GiB\n");
+            return SNAPPY_INVALID_INPUT;
+        }
+        chunks = snappy_hip_num_blocks(in_len, chunk_len);
+        capacity = snappy_hip_sz_compress_bound(in_len, chunk_len);
+        scratch_bytes = snappy_hip_sz_compress_scratch_bytes(chunk_len, 1, (uint32_t)chunks);
+    } else {
+        if (flags & ~SNAPPY_HIP_SZ_NO_VERIFY) return SNAPPY_INVALID_INPUT;
+        const char* why = in_len > SNAPPY_HIP_RAW_MAX_LEN ? "the file is longer than SNAPPY_HIP_RAW_MAX_LEN" : sz_host_walk(input->buffer, in_len, &chunks, &capacity);
+        if (!why && capacity > SNAPPY_HIP_RAW_MAX_LEN) why = "the plaintext is longer than SNAPPY_HIP_RAW_MAX_LEN";
+        if (why) {
+            (void)call.done_on_host();
+            fprintf(stderr, "snappy_hip: not a readable .sz stream: %s\n", why);
+            return SNAPPY_INVALID_INPUT;
+        }
+        scratch_bytes = snappy_hip_sz_decompress_scratch_bytes(1, (uint32_t)chunks);
+        if (snappy_status st = claim_output(output, capacity)) return st;
+    }
+    place(output, 0);
+    if (snappy_status st = call.need_device()) return st;
+
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    snappy_hip_raw_item* d_item = nullptr;
+    SzVerdict* d_verdict = nullptr;
+    if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_out, capacity}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict},
+                                         {&d_scratch, scratch_bytes}}))
+        return st;
+    const snappy_hip_raw_item item{d_in, in_len, d_out, capacity};
+    if (snappy_status st = call.upload({{d_in, input->buffer, in_len}, {d_item, &item, sizeof item}})) return st;
+    if (snappy_status st = call.launch("sz batch", [&] {
+            return compress ? snappy_hip_sz_compress_batch(d_item, 1, chunk_len, (uint32_t)chunks, &d_verdict->out_len, &d_verdict->status,
+                                                           d_verdict->result, d_scratch, scratch_bytes, nullptr)
+                            : snappy_hip_sz_decompress_batch(d_item, 1, (uint32_t)chunks, flags, &d_verdict->out_len, &d_verdict->status,
+                                                             &d_verdict->bad_chunk, d_verdict->result, d_scratch, scratch_bytes, nullptr);
+        }))
+        return st;
+    SzVerdict v{};
+    snappy_status verdict = SNAPPY_OK;
+    if (snappy_status st = call.copy_out([&]() -> int {
+            if (int rc = call.download({{&v, d_verdict, sizeof v}})) return rc;
+            if (v.status != SNAPPY_HIP_BLOCK_OK || v.out_len > capacity) {
+                if (!compress && (v.status == SNAPPY_HIP_SZ_CRC_MISMATCH || v.status == SNAPPY_HIP_BLOCK_INVALID))
+                    fprintf(stderr, "snappy_hip: data chunk %u of the .sz stream %s\n", v.bad_chunk,
+                            v.status == SNAPPY_HIP_SZ_CRC_MISMATCH ? "fails its CRC-32C" : "does not decode");
+                else
+                    fprintf(stderr, "snappy_hip: the .sz stream cannot be %s (status %u)\n", compress ? "written" : "decoded", v.status);
+                verdict = SNAPPY_INVALID_INPUT;
+                return 0;
+            }
+            if (compress && (verdict = claim_output(output, v.out_len))) return 0;
+            return call.download({{output->buffer, d_out, v.out_len}});
+        }))
+        return st;
+    if (verdict) return verdict;
+    if (snappy_status st = call.free_buffers()) return st;
+    place(output, v.out_len);
+    return SNAPPY_OK;
+}
+
 // Is a framed file intact (snappy_check_gpu)?  The header and the whole size chain on the host, the whole stream to the device,
 // one snappy_hip_check_blocks, 16 bytes back.  A broken header or chain is decided here: nothing is sent to the device.
 snappy_status check_gpu_body(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)
@@ -1286,6 +1395,18 @@ snappy_status snappy_decompress_raw_split_gpu(struct host_buffer_context* input,
                                               struct program_runtime* runtime)
 {
     return entry_guard([&] { return raw_gpu_body(false, input, output, 0, runtime, (int64_t)unit_len); });
+}
+
+snappy_status snappy_compress_sz_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t chunk_len,
+                                     struct program_runtime* runtime)
+{
+    return entry_guard([&] { return sz_gpu_body(true, input, output, chunk_len, 0, runtime); });
+}
+
+snappy_status snappy_decompress_sz_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t flags,
+                                       struct program_runtime* runtime)
+{
+    return entry_guard([&] { return sz_gpu_body(false, input, output, 0, flags, runtime); });
 }
 
 snappy_status snappy_check_gpu(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)

@@ -56,4 +56,11 @@ int launch_counted(hipStream_t st, Launch launch)
 // wavefronts of a persistent decode / check kernel whose work is counted on the device: K2's grid (SNAPPY_HIP_K2_WAVES)
 uint32_t range_grid_cap();
 
+// K1's LDS-table wavefronts outside snappy_hip.hip (the .sz compressor): the refusal of removed knobs (0, or fail(...)), whether
+// they run the stream form of the parse at this block size (else the bulk form), and how many of them, with lds_bytes of
+// dynamic LDS each, the device holds at once
+int check_k1_knobs();
+bool lds_table_stream_form(uint32_t block_size);
+uint32_t lds_table_resident_waves(uint32_t lds_bytes);
+
 }  // namespace snappy_hip_host

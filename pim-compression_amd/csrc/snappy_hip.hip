@@ -862,6 +862,9 @@ uint32_t snappy_hip_host::range_grid_cap()
     const int cap = std::max(1, env_int("SNAPPY_HIP_K2_WAVES", (int)shape.wave_slots()));
     return launch_shape::k2_launch_waves(shape, ~0ull, cap);
 }
+int snappy_hip_host::check_k1_knobs() { return check_knobs(); }
+bool snappy_hip_host::lds_table_stream_form(uint32_t block_size) { return (k1_stream_forms(block_size) & 1) != 0; }
+uint32_t snappy_hip_host::lds_table_resident_waves(uint32_t lds_bytes) { return launch_shape::update_resident_waves(device_shape(), lds_bytes); }
 extern "C" {
 
 uint64_t snappy_hip_decompress_ranges_scratch_bytes(uint32_t max_block_size, uint32_t range_count)

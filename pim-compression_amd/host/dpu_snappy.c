@@ -7,6 +7,8 @@
  *
  *   dpu_snappy [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
  *   dpu_snappy [-d] [-R [-S]] -T -i <input_file>
+ *   dpu_snappy [-d] [-c] -z [-b <chunk_len>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] -z -T -i <input_file>
  */
 #include <getopt.h>
 #include <limits.h>
@@ -25,9 +27,12 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
 	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] [-R [-S]] -T -i <input_file>\n", exe);
+	fprintf(stderr, "       %s [-d] [-c] -z [-b <chunk_len>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "       %s [-d] -z -T -i <input_file>\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
+	fprintf(stderr, "z: the Snappy framing format (.sz, what snzip and the stream classes of other Snappy libraries write): chunks of <block_size> bytes, each with the CRC-32C of its plain bytes, which decompression compares; with -T: decode the file, compare every CRC, write nothing\n");
 	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S; with -d -R -T (no <unit_len>): check one large raw stream with many wavefronts, whatever built it\n");
 	fprintf(stderr, "W: with -d, decompressing a block-framed file: put a workgroup of <waves> wavefronts (2, 4, 8 or 16, default 16) on every block instead of one wavefront; for small files\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
@@ -109,6 +114,7 @@ int main(int argc, char **argv)
 	unsigned long long write_off = 0;
 	const char *patch_path = NULL;
 	int raw = 0;
+	int sz = 0;
 	int use_keep = 0;
 	unsigned long long keep_len = 0;
 	const char *tail_path = NULL;
@@ -118,7 +124,7 @@ int main(int argc, char **argv)
 	int split_has_unit = 0;
 	int use_wide = 0;
 	unsigned long wide_waves = 0;
-	while ((opt = getopt(argc, argv, "dcRTS::W::b:g:i:o:r:w:t:a:")) != -1) {
+	while ((opt = getopt(argc, argv, "dcRzTS::W::b:g:i:o:r:w:t:a:")) != -1) {
 		switch (opt) {
 		case 'S': {                  /* -S, -S<unit_len> or -S <unit_len> */
 			const char *arg = optarg;
@@ -192,6 +198,7 @@ int main(int argc, char **argv)
 		case 'd': use_gpu = 1; break;
 		case 'c': compress = 1; break;
 		case 'R': raw = 1; break;
+		case 'z': sz = 1; break;
 		case 'b': block_size = atoi(optarg); break;
 		case 'g': setenv("SNAPPY_HIP_NUM_GPUS", optarg, 1); break;
 		case 'i': in_path = optarg; break;
@@ -215,6 +222,10 @@ int main(int argc, char **argv)
 	}
 	if (raw && (use_range || use_write)) {
 		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
+		return -2;
+	}
+	if (sz && (raw || use_range || use_write || use_split || use_wide || use_keep || tail_path)) {
+		fprintf(stderr, "-z reads and writes one .sz stream: it goes with -c, -b, -d and -T only\n");
 		return -2;
 	}
 	if (use_split && (!raw || compress)) {
@@ -263,6 +274,36 @@ int main(int argc, char **argv)
 	memset(&rt, 0, sizeof(rt));                              /* the reference leaves this uninitialised */
 	snappy_status st;
 	struct timeval t0, t1;
+	if (sz && use_check) {
+		/* the CRCs are over the plaintext: the file is decoded (into a buffer that is dropped), every CRC compared */
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		if (use_gpu) {
+			st = snappy_decompress_sz_gpu(&input, &output, 0, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = snappy_decompress_sz_host(&input, &output, 0);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+		if (st == SNAPPY_BUFFER_TOO_SMALL) {
+			fprintf(stderr, "Encountered Snappy error %u\n", st);
+			return -1;
+		}
+		if (st == SNAPPY_OK)
+			printf("Check: OK, %lu bytes\n", (unsigned long)output.length);
+		else
+			printf("Check: INVALID\n");
+		printf("Pre-processing time: %f\n", rt.pre);
+		printf("Alloc time: %f\n", rt.d_alloc);
+		printf("Load time: %f\n", rt.load);
+		printf("Copy in time: %f\n", rt.copy_in);
+		printf("Host time: %f\n", rt.run);
+		printf("Copy out time: %f\n", rt.copy_out);
+		printf("Free time: %f\n", rt.d_free);
+		return st == SNAPPY_OK ? 0 : 1;
+	}
 	if (use_check) {
 		/* nothing is decoded to anywhere: the verdict, one line, the exit status */
 		snappy_hip_check_report rep = { 0, 0, 0, 0 };
@@ -299,7 +340,20 @@ int main(int argc, char **argv)
 		printf("Free time: %f\n", rt.d_free);
 		return st == SNAPPY_OK ? 0 : 1;
 	}
-	if (raw) {
+	if (sz) {
+		/* one .sz stream, either way; both modes allocate the output */
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		if (use_gpu) {
+			st = compress ? snappy_compress_sz_gpu(&input, &output, (uint32_t)block_size, &rt) : snappy_decompress_sz_gpu(&input, &output, 0, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = compress ? snappy_compress_sz_host(&input, &output, (uint32_t)block_size) : snappy_decompress_sz_host(&input, &output, 0);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+	} else if (raw) {
 		/* one raw Snappy stream, either way; in -d mode one item through the batch calls of the library, which allocates
 		 * the output */
 		if (use_gpu) {

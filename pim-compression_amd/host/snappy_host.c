@@ -343,6 +343,195 @@ snappy_status snappy_decompress_raw_host(struct host_buffer_context *input, stru
 	return (op == out_end) ? SNAPPY_OK : SNAPPY_INVALID_INPUT;
 }
 
+/* ---- the Snappy framing format (dpu_snappy -z) -------------------------------- */
+
+/* CRC-32C (Castagnoli, reflected 0x82F63B78, init and final xor 0xffffffff) by a byte table made on first use */
+static uint32_t crc32c_host(const uint8_t *p, unsigned long n)
+{
+	static uint32_t table[256];
+	if (!table[1])
+		for (uint32_t b = 0; b < 256; b++) {
+			uint32_t c = b;
+			for (int k = 0; k < 8; k++)
+				c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
+			table[b] = c;
+		}
+	uint32_t c = 0xffffffffu;
+	while (n--)
+		c = (c >> 8) ^ table[(c ^ *p++) & 0xff];
+	return ~c;
+}
+
+static uint32_t crc_mask_host(uint32_t c)
+{
+	return ((c >> 15) | (c << 17)) + 0xa282ead8u;
+}
+
+static void put32(uint8_t *p, uint32_t v)
+{
+	p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+}
+
+/* The bytes snappy_hip_sz_compress_batch writes: the identifier, then per chunk_len bytes one chunk -- type 0x00 with
+ * varint(n) + host_compress_block's elements iff those are shorter than the n plain bytes, else type 0x01 with the plain
+ * bytes -- behind the masked CRC-32C of the plain bytes.  output->buffer is malloc'd here (the exact bound). */
+snappy_status snappy_compress_sz_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t chunk_len)
+{
+	if (chunk_len < 64 || chunk_len > 65535 || input->length > 0xffffffffUL)
+		return SNAPPY_INVALID_INPUT;
+	const unsigned long chunks = (input->length + chunk_len - 1) / chunk_len;
+	const unsigned long cap = 10 + 8 * chunks + input->length;
+	uint16_t *tab = malloc(TABLE_MAX * sizeof(*tab));
+	uint8_t *slot = malloc(4 + 32 + (unsigned long)chunk_len + chunk_len / 6 + 8);
+	output->buffer = malloc(cap);
+	if (!tab || !slot || !output->buffer) {
+		free(tab);
+		free(slot);
+		return SNAPPY_BUFFER_TOO_SMALL;
+	}
+	uint8_t *op = output->buffer;
+	memcpy(op, "\xff\x06\x00\x00sNaPpY", 10);
+	op += 10;
+	const uint8_t *in = input->buffer;
+	unsigned long left = input->length;
+	while (left) {
+		const uint32_t n = left < chunk_len ? (uint32_t)left : chunk_len;
+		struct sink s = { slot };
+		host_compress_block(in, n, &s, tab);
+		const uint32_t elements = (uint32_t)(s.p - slot) - 4;
+		uint8_t var[5];
+		const uint32_t vlen = (uint32_t)(varint_put(var, n) - var);
+		const int compressed = vlen + elements < n;
+		const uint32_t L = 4 + (compressed ? vlen + elements : n);
+		put32(op, (uint32_t)(compressed ? 0x00 : 0x01) | (L << 8));
+		put32(op + 4, crc_mask_host(crc32c_host(in, n)));
+		if (compressed) {
+			memcpy(op + 8, var, vlen);
+			memcpy(op + 8 + vlen, slot + 4, elements);
+		} else {
+			memcpy(op + 8, in, n);
+		}
+		op += 4 + L;
+		in += n;
+		left -= n;
+	}
+	free(tab);
+	free(slot);
+	input->curr = input->buffer + input->length;
+	output->curr = op;
+	output->length = (unsigned long)(op - output->buffer);
+	return SNAPPY_OK;
+}
+
+/* The chunk chain of a whole .sz file by the rules of snappy_hip_sz_decompress_batch: the sum of the data chunks' uncompressed
+ * lengths, or why the stream is refused.  Reads nothing outside [buf, buf + len). */
+static snappy_status sz_walk_host(const uint8_t *buf, unsigned long len, uint64_t *total)
+{
+	unsigned long at = 0;
+	int identified = 0;
+	*total = 0;
+	while (at < len) {
+		if (len - at < 4) {
+			fprintf(stderr, "a chunk header runs past the end of the file\n");
+			return SNAPPY_INVALID_INPUT;
+		}
+		const uint32_t type = buf[at], L = buf[at + 1] | (uint32_t)buf[at + 2] << 8 | (uint32_t)buf[at + 3] << 16;
+		if (len - at - 4 < L) {
+			fprintf(stderr, "the chunk at offset %lu runs past the end of the file\n", at);
+			return SNAPPY_INVALID_INPUT;
+		}
+		const uint8_t *body = buf + at + 4;
+		if (type == 0xff) {
+			if (L != 6 || memcmp(body, "sNaPpY", 6) != 0) {
+				fprintf(stderr, "a wrong stream identifier at offset %lu\n", at);
+				return SNAPPY_INVALID_INPUT;
+			}
+			identified = 1;
+		} else if (!identified) {
+			fprintf(stderr, "the first chunk is not the stream identifier\n");
+			return SNAPPY_INVALID_INPUT;
+		} else if (type <= 1) {
+			uint32_t n = L - 4;
+			if (L < 4) {
+				fprintf(stderr, "the data chunk at offset %lu has no room for its checksum\n", at);
+				return SNAPPY_INVALID_INPUT;
+			}
+			if (type == 0) {
+				const uint8_t *p = varint_get(body + 4, body + L, &n);
+				if (!p || (p - (body + 4) == 5 && p[-1] >= 16)) {
+					fprintf(stderr, "the compressed chunk at offset %lu has no readable length\n", at);
+					return SNAPPY_INVALID_INPUT;
+				}
+			}
+			if (n > 65536) {
+				fprintf(stderr, "the chunk at offset %lu holds more than 65536 bytes\n", at);
+				return SNAPPY_INVALID_INPUT;
+			}
+			*total += n;
+		} else if (type < 0x80) {
+			fprintf(stderr, "reserved unskippable chunk 0x%02x at offset %lu\n", type, at);
+			return SNAPPY_INVALID_INPUT;
+		}
+		at += 4ul + L;
+	}
+	if (!identified) {
+		fprintf(stderr, "no stream identifier\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	return SNAPPY_OK;
+}
+
+/* A whole .sz file (input->buffer at its first byte) decoded into output->buffer, malloc'd here; every chunk's CRC compared
+ * unless no_verify.  A chain that does not parse, a chunk that does not decode to its stated length or fails its CRC:
+ * SNAPPY_INVALID_INPUT, no output. */
+snappy_status snappy_decompress_sz_host(struct host_buffer_context *input, struct host_buffer_context *output, int no_verify)
+{
+	const uint8_t *buf = input->buffer;
+	const unsigned long len = input->length;
+	uint64_t total;
+	output->buffer = NULL;
+	output->length = 0;
+	if (sz_walk_host(buf, len, &total) != SNAPPY_OK)
+		return SNAPPY_INVALID_INPUT;
+	if (total > output->max)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	uint8_t *out = malloc(total ? total : 1);
+	if (!out)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	uint8_t *op = out;
+	unsigned long at = 0, k = 0;
+	while (at < len) {                                     /* (the walk above has checked every bound used here) */
+		const uint32_t type = buf[at], L = buf[at + 1] | (uint32_t)buf[at + 2] << 8 | (uint32_t)buf[at + 3] << 16;
+		const uint8_t *body = buf + at + 4;
+		if (type <= 1) {
+			uint32_t n = L - 4;
+			if (type == 0) {
+				const uint8_t *ip = varint_get(body + 4, body + L, &n);
+				if (decompress_block_host(ip, body + L, op, op, op + n) != op + n) {
+					fprintf(stderr, "data chunk %lu at offset %lu does not decode\n", k, at);
+					free(out);
+					return SNAPPY_INVALID_INPUT;
+				}
+			} else {
+				memcpy(op, body + 4, n);
+			}
+			if (!no_verify && crc_mask_host(crc32c_host(op, n)) != load32(body)) {
+				fprintf(stderr, "data chunk %lu at offset %lu fails its CRC-32C\n", k, at);
+				free(out);
+				return SNAPPY_INVALID_INPUT;
+			}
+			op += n;
+			k++;
+		}
+		at += 4ul + L;
+	}
+	input->curr = input->buffer + len;
+	output->buffer = out;
+	output->curr = op;
+	output->length = (unsigned long)total;
+	return SNAPPY_OK;
+}
+
 /* ---- the check (dpu_snappy -T) ---------------------------------------------- */
 
 snappy_status snappy_check_host(const struct host_buffer_context *input, snappy_hip_check_report *report)

@@ -39,6 +39,11 @@ snappy_status snappy_decompress_raw_host(struct host_buffer_context *input, stru
 snappy_status snappy_check_host(const struct host_buffer_context *input, snappy_hip_check_report *report);
 /* dpu_snappy -T -R: the same for one raw Snappy stream (decoded into a scratch buffer of the header's length) */
 snappy_status snappy_check_raw_host(const struct host_buffer_context *input, uint64_t *uncompressed_len);
+/* dpu_snappy -z: the Snappy framing format (.sz).  Compression writes, byte for byte, what snappy_hip_sz_compress_batch writes
+ * for the same input and chunk_len (64..65535 here, as -b everywhere in host mode); decompression takes streams of any writer,
+ * by the device's rules, and compares every chunk's CRC-32C unless no_verify.  Both malloc output->buffer. */
+snappy_status snappy_compress_sz_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t chunk_len);
+snappy_status snappy_decompress_sz_host(struct host_buffer_context *input, struct host_buffer_context *output, int no_verify);
 double get_runtime(struct timeval *start, struct timeval *end);
 
 #ifdef __cplusplus

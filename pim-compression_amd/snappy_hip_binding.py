@@ -136,6 +136,24 @@ def lib():
         L.snappy_hip_raw_compress_scratch_bytes.argtypes = [u32, u32, u32]
         L.snappy_hip_raw_compress_batch.restype = ctypes.c_int
         L.snappy_hip_raw_compress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_crc32c_batch.restype = ctypes.c_int
+        L.snappy_hip_crc32c_batch.argtypes = [vp, u32, vp, vp]
+        L.snappy_hip_sz_decompress_scratch_bytes.restype = u64
+        L.snappy_hip_sz_decompress_scratch_bytes.argtypes = [u32, u32]
+        L.snappy_hip_sz_decompress_batch.restype = ctypes.c_int
+        L.snappy_hip_sz_decompress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_sz_compress_bound.restype = u64
+        L.snappy_hip_sz_compress_bound.argtypes = [u64, u32]
+        L.snappy_hip_sz_compress_scratch_bytes.restype = u64
+        L.snappy_hip_sz_compress_scratch_bytes.argtypes = [u32, u32, u32]
+        L.snappy_hip_sz_compress_batch.restype = ctypes.c_int
+        L.snappy_hip_sz_compress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp]
+        L.snappy_compress_sz_gpu.restype = ctypes.c_int
+        L.snappy_compress_sz_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                             ctypes.POINTER(ProgramRuntime)]
+        L.snappy_decompress_sz_gpu.restype = ctypes.c_int
+        L.snappy_decompress_sz_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                               ctypes.POINTER(ProgramRuntime)]
         L.snappy_hip_check_scratch_bytes.restype = u64
         L.snappy_hip_check_scratch_bytes.argtypes = [u32]
         L.snappy_hip_check_blocks.restype = ctypes.c_int
@@ -580,6 +598,71 @@ def raw_compress_batch(d_items, count, block_size, max_fragments, d_out_len, d_s
     return d_scratch
 
 
+# the Snappy framing format (.sz) and CRC-32C (snappy_hip_sz_decompress_batch / snappy_hip_sz_compress_batch / snappy_hip_crc32c_batch)
+SZ_CRC_MISMATCH = 7
+SZ_UNSUPPORTED = 8
+SZ_NO_VERIFY = 1
+CRC_ITEM_DTYPE = np.dtype([("src", "<u8"), ("src_len", "<u8")])   # snappy_hip_crc_item
+
+
+def make_crc_items(entries, device="cuda"):
+    """entries: list of (src, src_len) with src a device address (int, 0 = null) -> device tensor of snappy_hip_crc_item."""
+    import torch
+    arr = np.zeros(max(len(entries), 1), dtype=CRC_ITEM_DTYPE)
+    for i, e in enumerate(entries):
+        arr[i] = tuple(e)
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
+def crc32c_batch(d_items, count, d_crc):
+    """Enqueue snappy_hip_crc32c_batch on the current stream: d_crc[i] (device int32 tensor of `count` entries) = the unmasked
+    CRC-32C of item i.  Nothing is synchronised."""
+    import torch
+    _check(lib().snappy_hip_crc32c_batch(d_items.data_ptr(), count, d_crc.data_ptr(), _stream_handle(torch)), "snappy_hip_crc32c_batch")
+
+
+def sz_decompress_scratch_bytes(count, max_chunks):
+    """Scratch of snappy_hip_sz_decompress_batch."""
+    return int(lib().snappy_hip_sz_decompress_scratch_bytes(count, max_chunks))
+
+
+def sz_decompress_batch(d_items, count, max_chunks, d_out_len, d_status, d_bad_chunk, d_result, flags=0, d_scratch=None):
+    """Enqueue snappy_hip_sz_decompress_batch on the current stream.  d_items: make_raw_items() tensor, each src one .sz stream.
+    d_out_len: device int64 tensor, d_status and d_bad_chunk: device int32 tensors of `count` entries, d_result: device int32
+    tensor of two (chunks the batch needs, items OK).  flags: SZ_NO_VERIFY skips the CRC comparison.  d_scratch: 256-byte
+    aligned device uint8 tensor (default: a fresh one).  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(sz_decompress_scratch_bytes(count, max_chunks), 256), dtype=torch.uint8, device=d_result.device)
+    _check(lib().snappy_hip_sz_decompress_batch(d_items.data_ptr() if count else None, count, max_chunks, flags, d_out_len.data_ptr() if count else None,
+                                                d_status.data_ptr() if count else None, d_bad_chunk.data_ptr() if count else None,
+                                                d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(), _stream_handle(torch)),
+           "snappy_hip_sz_decompress_batch")
+    return d_scratch
+
+
+def sz_compress_bound(src_len, chunk_len):
+    """10 + 8 * chunks + src_len: a dst_capacity that always suffices, exact when nothing compresses (0 for a bad chunk_len)."""
+    return int(lib().snappy_hip_sz_compress_bound(src_len, chunk_len))
+
+
+def sz_compress_scratch_bytes(chunk_len, count, max_chunks):
+    """Scratch of snappy_hip_sz_compress_batch (0 for a bad chunk_len)."""
+    return int(lib().snappy_hip_sz_compress_scratch_bytes(chunk_len, count, max_chunks))
+
+
+def sz_compress_batch(d_items, count, chunk_len, max_chunks, d_out_len, d_status, d_result, d_scratch=None):
+    """Enqueue snappy_hip_sz_compress_batch on the current stream: item i's plaintext as one .sz stream of chunk_len chunks.
+    Arrays as in raw_compress_batch.  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(sz_compress_scratch_bytes(chunk_len, count, max_chunks), 256), dtype=torch.uint8, device=d_result.device)
+    _check(lib().snappy_hip_sz_compress_batch(d_items.data_ptr() if count else None, count, chunk_len, max_chunks,
+                                              d_out_len.data_ptr() if count else None, d_status.data_ptr() if count else None, d_result.data_ptr(),
+                                              d_scratch.data_ptr(), d_scratch.numel(), _stream_handle(torch)), "snappy_hip_sz_compress_batch")
+    return d_scratch
+
+
 # checking without decoding (snappy_hip_check_blocks, snappy_hip_raw_check_batch)
 CHECK_NONE = 0xffffffff
 
@@ -816,6 +899,16 @@ def raw_compress_host(data, block_size=32768, out_capacity=None):
 def raw_decompress_host(stream, out_capacity=None):
     """snappy_decompress_raw_gpu on a whole raw Snappy stream held in host memory -> (status, plaintext, runtime dict)."""
     return _raw_host(lambda i, o, r: lib().snappy_decompress_raw_gpu(i, o, r), stream, out_capacity)
+
+
+def sz_compress_host(data, chunk_len=32768, out_capacity=None):
+    """snappy_compress_sz_gpu on a host buffer -> (status, .sz stream, runtime dict).  out_capacity: as in compress_host."""
+    return _raw_host(lambda i, o, r: lib().snappy_compress_sz_gpu(i, o, chunk_len, r), data, out_capacity)
+
+
+def sz_decompress_host(stream, flags=0, out_capacity=None):
+    """snappy_decompress_sz_gpu on a whole .sz stream held in host memory -> (status, plaintext, runtime dict)."""
+    return _raw_host(lambda i, o, r: lib().snappy_decompress_sz_gpu(i, o, flags, r), stream, out_capacity)
 
 
 def check_host(stream):
