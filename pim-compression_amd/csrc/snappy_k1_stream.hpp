@@ -37,16 +37,7 @@
 
 namespace snappy_hip {
 
-#ifdef SNAPPY_EMU
-// emulator statistics: [0] windows taken, [1] windows sent back (stride widened), [2] copies of 64+ bytes, [3] stop lanes settled,
-// [4] stream_run calls, [5] bulk_run calls from the stream form, [6] settled with the ballot (chains, hidden lanes, fallback),
-// [7] windows whose duplicate analysis fell back to the race tables, [8] matches extended past the compared bytes,
-// [9] settled from the partner lane, [10] settled from the gathered entry
-inline unsigned long long g_stream_stats[16] = {0};
-#define STREAM_STAT(i) do { if (lane == 0) ++g_stream_stats[i]; } while (0)
-#else
-#define STREAM_STAT(i) ((void)0)
-#endif
+// (the emulator statistics, g_stream_stats / STREAM_STAT, are defined in snappy_kernels.hpp: bulk_run() counts into them too)
 
 // -DSNAPPY_PROF (tools/prof_stream.py): lap timers around the phases of the stream form, summed into g_prof by the lanes.
 // Every cycle of a block lands in exactly one bucket; the counts are the number of laps.  Not defined in a product build.
@@ -343,9 +334,10 @@ __device__ __forceinline__ void stream_emit(uint8_t* __restrict__ dst, const uin
                                             unsigned long long COV, bool by_copy, uint32_t r_out, bool long_copy, uint32_t ip,
                                             uint32_t long_cand, uint32_t long_len, uint32_t lane)
 {
-    if (H) emit_segment(dst, blk, op, next_emit, base, x0, ent, extv, H, COV, by_copy, r_out, lane);
+    // (<false>: the stride-1 scan leaves no literal of 1 KiB pending -- emit_literal)
+    if (H) emit_segment<false>(dst, blk, op, next_emit, base, x0, ent, extv, H, COV, by_copy, r_out, lane);
     if (long_copy) {
-        if (ip > next_emit) op = emit_literal_windowed(dst, op, blk, next_emit, ip - next_emit, base, x0, lane);
+        if (ip > next_emit) op = emit_literal_windowed<false>(dst, op, blk, next_emit, ip - next_emit, base, x0, lane);
         op = emit_copy(dst, op, ip - long_cand, long_len, lane);
         next_emit = ip + long_len;
     }

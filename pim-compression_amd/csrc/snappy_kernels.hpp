@@ -58,7 +58,9 @@ __device__ __forceinline__ uint32_t table_entries_for(uint32_t n)
 // element emitters (snappy_compress.c:202-272); `op` is the byte offset in the slot
 // ---------------------------------------------------------------------------
 
-// snappy_compress.c:202-225
+// snappy_compress.c:202-225.  kWide = false leaves out the 16-byte copy of long literals: the stream form's emission, where no
+// long literal is ever pending (it takes over behind a copy) and the copy's registers would cost the kernel a wavefront per SIMD
+template <bool kWide = true>
 __device__ __forceinline__ uint32_t emit_literal(uint8_t* __restrict__ dst, uint32_t op,
                                                  const uint8_t* __restrict__ src, uint32_t len, uint32_t lane)
 {
@@ -76,6 +78,27 @@ __device__ __forceinline__ uint32_t emit_literal(uint8_t* __restrict__ dst, uint
     uint8_t* d = dst + op + hdr;
     if (len <= kWave) {
         if (lane < len) d[lane] = src[lane];
+    } else if (kWide && len >= 1024u) {
+        // a long literal (an incompressible stretch, up to the whole block): 16 bytes per lane; 4 KiB per trip with its four
+        // loads in flight before the first store, then what is left (< 4 KiB) in steps of 1 KiB whose offsets are clamped
+        // back, so that the last store ends exactly at `len` (it rewrites bytes with the same values) -- the literal copy of
+        // a raw stream in k2_decode_block does the same
+        uint32_t base = 0;
+        for (; base + 64u * kWave <= len; base += 64u * kWave) {
+            const uint8_t* __restrict__ s = src + (base + 16u * lane);
+            uint8_t* __restrict__ t = d + (base + 16u * lane);
+            const uint4 v0 = ld128(s), v1 = ld128(s + 16u * kWave), v2 = ld128(s + 32u * kWave), v3 = ld128(s + 48u * kWave);
+            st128(t, v0);
+            st128(t + 16u * kWave, v1);
+            st128(t + 32u * kWave, v2);
+            st128(t + 48u * kWave, v3);
+        }
+        const uint32_t last = len - 16u;
+        for (; base < len; base += 16u * kWave) {
+            const uint32_t i = base + 16u * lane;
+            const uint32_t o = i < last ? i : last;
+            st128(d + o, ld128(src + o));
+        }
     } else {
         uint32_t i = 4 * lane;
         for (; i + 4 <= len; i += 4 * kWave) st32(d + i, ld32(src + i));
@@ -301,6 +324,19 @@ __device__ __forceinline__ void emu_check_distinct_stores(bool stores, uint32_t 
 __device__ __forceinline__ void emu_check_distinct_stores(bool, uint32_t, uint32_t) {}
 #endif
 
+#ifdef SNAPPY_EMU
+// emulator statistics: [0] windows taken, [1] windows sent back (stride widened), [2] copies of 64+ bytes, [3] stop lanes settled,
+// [4] stream_run calls, [5] bulk_run calls from the stream form, [6] settled with the ballot (chains, hidden lanes, fallback),
+// [7] windows whose duplicate analysis fell back to the race tables, [8] matches extended past the compared bytes,
+// [9] settled from the partner lane, [10] settled from the gathered entry (0-10: the stream form, snappy_k1_stream.hpp);
+// bulk_run()'s strided scan batches: [11] batches evaluated, closed [12] by a hit, [13] by a shared slot, [14] by the limit,
+// [15] not at all (64 misses)
+inline unsigned long long g_stream_stats[16] = {0};
+#define STREAM_STAT(i) do { if (lane == 0) ++g_stream_stats[i]; } while (0)
+#else
+#define STREAM_STAT(i) ((void)0)
+#endif
+
 // TaggedGlobalTable behind a one-bit-per-slot "written in this block" filter in LDS (2 KiB per wavefront).  Early in a
 // block most slots still hold the initial entry (candidate position 0, :145 + :346), and the speculative gathers of the
 // look-ahead forms read 64 slots per 64 input bytes -- one random 64-byte HBM line per input byte, which is what bounds
@@ -472,11 +508,12 @@ __device__ __forceinline__ uint32_t emit_copy_packed(uint8_t* __restrict__ dst, 
 }
 
 // snappy_compress.c:202-225 with the payload taken from the window when [from, from+len) lies inside it
+template <bool kWide = true>
 __device__ __forceinline__ uint32_t emit_literal_windowed(uint8_t* __restrict__ dst, uint32_t op,
                                                           const uint8_t* __restrict__ blk, uint32_t from, uint32_t len,
                                                           uint32_t win_base, uint32_t win_x0, uint32_t lane)
 {
-    if (from < win_base || from + len > win_base + kWave) return emit_literal(dst, op, blk + from, len, lane);
+    if (from < win_base || from + len > win_base + kWave) return emit_literal<kWide>(dst, op, blk + from, len, lane);
     const uint32_t n = len - 1;                                  // len <= 64 here, so n < 64
     uint32_t hdr;
     if (n < 60) {
@@ -556,6 +593,118 @@ __device__ __forceinline__ unsigned long long dup_slot_lanes(lds_bytes_t scratch
     const uint32_t mb = scratch[sb];
     __builtin_amdgcn_wave_barrier();
     return __ballot(ma == 0xff && mb == 0xff);
+}
+// The same among the lanes with `on` set: the others claim no byte and are not reported.  All lanes call.
+__device__ __forceinline__ unsigned long long dup_slot_lanes_among(lds_bytes_t scratch, uint32_t h, bool on, uint32_t lane)
+{
+    const uint32_t sa = h & (kDupSlots / 2 - 1);
+    const uint32_t sb = kDupSlots / 2 + ((h >> 5) & (kDupSlots / 2 - 1));
+    if (on) {
+        scratch[sa] = (uint8_t)lane;
+        scratch[sb] = (uint8_t)lane;
+    }
+    __builtin_amdgcn_wave_barrier();
+    uint32_t wa = lane, wb = lane;
+    if (on) {
+        wa = scratch[sa];
+        wb = scratch[sb];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (wa != lane) scratch[sa] = 0xff;              // (only a lane that is `on` can have lost)
+    if (wb != lane) scratch[sb] = 0xff;
+    __builtin_amdgcn_wave_barrier();
+    uint32_t ma = 0, mb = 0;
+    if (on) {
+        ma = scratch[sa];
+        mb = scratch[sb];
+    }
+    __builtin_amdgcn_wave_barrier();
+    return __ballot(ma == 0xff && mb == 0xff);
+}
+
+// ---------------------------------------------------------------------------
+// K1, strided scan batch.  Where the reference's skip heuristic (:336-348) has widened the stride, the scan probes one
+// position in `stride` and almost never hits: incompressible data.  The state in front of a probe is (ip, skip); the probes
+// that follow it, for as long as none hits, are known in closed form -- probe k is made with s_k = skip + k at stride
+// s_k >> 5 -- so 64 of them are made at once, lane k making probe k:
+//     p_0 = ip, p_{k+1} = p_k + (s_k >> 5)        (at most three stride levels in 64 probes)
+//     lane k is LIVE iff p_k + (s_k >> 5) <= limit  (:342-343: the scan ends before the table is touched)
+// Every live lane reads its table slot and its candidate's 4 bytes.  Let m be the first lane that hits, that shares its slot
+// with an EARLIER live lane (its read would have to see that lane's insert), or that is not live.  Lanes [0, m) are misses
+// with slots of their own, and none of them shares a slot with a lane in front of it: each read what the reference reads, and
+// one masked store inserts them all (distinct addresses, so their order does not matter).  Returns m; the reference's state
+// is then (p_m, skip + m) -- returned in ip_out -- and whatever lane m is, the caller's code settles it from there.
+// m == 0 (lane 0 hits) leaves the table untouched.  Earlier batches' stores are ordered before these loads: vector memory
+// operations of one wavefront complete in order (the guarantee CachedGlobalTable::store_masked relies on).
+// ---------------------------------------------------------------------------
+template <class Table>
+__device__ __forceinline__ uint32_t strided_scan_batch(const Table& table, const uint8_t* __restrict__ blk, uint32_t shift,
+                                                       uint32_t limit, uint32_t ip, uint32_t skip, lds_bytes_t dup_scratch,
+                                                       uint32_t lane, uint32_t& ip_out, bool& again)
+{
+    const uint32_t stride0 = skip >> 5;
+    const uint32_t c0 = 32u - (skip & 31u);          // probes left at the first stride level (1..32)
+    const uint32_t over0 = lane > c0 ? lane - c0 : 0u;
+    const uint32_t over1 = lane > c0 + 32u ? lane - c0 - 32u : 0u;
+    const uint32_t pk = ip + lane * stride0 + over0 + over1;
+    const uint32_t stride_k = (skip + lane) >> 5;
+    const bool live = pk + stride_k <= limit;        // (lane 0 is: the caller has checked ip + stride <= limit)
+    const unsigned long long livem = __ballot(live);
+    const uint32_t x = ld32(blk + (live ? pk : ip)); // live: pk + 4 <= limit + 15 = the block's length
+    const uint32_t prod = x * kHashMul;              // :161-166
+    const uint32_t h = prod >> shift;
+    const uint32_t mine = ((prod << (32 - shift)) & 0xffff0000u) | pk;
+    uint32_t ent = 0;
+    if (live) ent = table.load_lane(h, mine);
+    const unsigned long long dupm = dup_slot_lanes_among(dup_scratch, h, live, lane);
+    const bool worth = live && !Table::certain_miss(ent, mine);
+    uint32_t k0 = 0;
+    if (worth) k0 = ld32(blk + (ent & 0xffffu));     // every stored position p has p + 16 <= block length
+    const unsigned long long hitm = __ballot(worth) & __ballot(k0 == x);
+    // the first stop.  dup_slot_lanes reports a superset of the lanes that share a slot with ANY live lane; the first lane of
+    // such a group has nothing in front of it and is no stop -- asked lane by lane (rare: a pair in one batch in ten)
+    unsigned long long stops = hitm | dupm | ~livem;
+    uint32_t m;
+    again = true;                                    // another batch from lane m on can make progress (lane m is no hit)
+    STREAM_STAT(11);
+    for (;;) {
+        m = ctz64_or(stops, kWave);
+        if (m == kWave) {
+            STREAM_STAT(15);
+            break;
+        }
+        if (!((livem >> m) & 1ull)) {
+            STREAM_STAT(14);
+            break;
+        }
+        if ((dupm >> m) & 1ull) {
+            const uint32_t hm = (uint32_t)__builtin_amdgcn_readlane((int)h, (int)m);
+            if (m && (__ballot(h == hm) & livem & lane_range(0, m))) {
+                STREAM_STAT(13);                     // (in front of the next batch it shares with nobody)
+                break;
+            }
+        }
+        if ((hitm >> m) & 1ull) {
+            STREAM_STAT(12);
+            again = false;
+            break;
+        }
+        stops &= ~(1ull << m);
+    }
+    ip_out = m < kWave ? (uint32_t)__builtin_amdgcn_readlane((int)pk, (int)m)
+                       : (uint32_t)__builtin_amdgcn_readlane((int)pk, 63) + ((skip + 63u) >> 5);
+    if (m) {
+        const unsigned long long cm = lane_range(0, m);
+        if constexpr (Table::kCollectiveStore) {
+            table.store_masked(cm, h, pk, lane);
+        } else {
+            const bool s = __builtin_amdgcn_inverse_ballot_w64(cm);
+            if (s) table.store_lane(h, mine);
+            emu_check_distinct_stores(s, h, lane);
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    return m;
 }
 
 template <class Table, uint32_t kChunk>
@@ -700,6 +849,7 @@ __device__ __forceinline__ unsigned long long lanes_below(uint32_t n) { return ~
 //     P(l) = op + #literal bytes + 2 * #copies + #3-byte copies + #literal headers   (all counted below lane l)
 // literal lanes store their byte (byte 0 of x0 IS block byte base + l), run-start lanes the literal header, hit lanes the
 // 2- or 3-byte copy element.
+template <bool kWide = true>
 __device__ __forceinline__ void emit_segment(uint8_t* __restrict__ dst, const uint8_t* __restrict__ blk, uint32_t& op, uint32_t& next_emit,
                                              uint32_t base, uint32_t x0, uint32_t ent, uint32_t extv, unsigned long long H,
                                              unsigned long long COV, bool by_copy, uint32_t r, uint32_t lane)
@@ -712,7 +862,7 @@ __device__ __forceinline__ void emit_segment(uint8_t* __restrict__ dst, const ui
     if (next_emit >= base && p0 - next_emit <= 60u) {
         s0 = next_emit - base;                       // the first run is inside the window too
     } else if (p0 > next_emit) {                     // it started in an earlier window (or is 61+ bytes)
-        op = emit_literal_windowed(dst, op, blk, next_emit, p0 - next_emit, base, x0, lane);
+        op = emit_literal_windowed<kWide>(dst, op, blk, next_emit, p0 - next_emit, base, x0, lane);
     }
     const unsigned long long LIT = ((~0ull << s0) & lanes_below(last_end)) & ~COV;
     const unsigned long long LS = LIT & ~(LIT << 1);            // first lane of each literal run
@@ -847,6 +997,7 @@ __device__ __forceinline__ bool bulk_run(const uint8_t* __restrict__ blk, uint32
         State st;
         uint32_t ip = ps.ip;
         uint32_t skip = ps.skip;
+        bool batch_ok = true;                                    // false: the last batch ended on a hit, which is next
         for (uint32_t iter = 0;; ++iter) {
             const uint32_t stride = skip >> 5;
             const uint32_t step = stride ? stride : 1u;
@@ -855,6 +1006,20 @@ __device__ __forceinline__ bool bulk_run(const uint8_t* __restrict__ blk, uint32
                 finished = false;
                 break;
             }
+            if (!kAtWindowEntry && stride >= 2u && batch_ok) {
+                // the scan has widened its stride (:339): 64 probes at once for as long as they miss (strided_scan_batch).
+                // A hit is settled below, one probe from the reference's exact state (m == 0: at once); a lane that shares a
+                // slot with an earlier one is lane 0 of the next batch; the limit ends the scan at the top of the loop.
+                uint32_t ip_m;
+                const uint32_t m = strided_scan_batch(table, blk, shift, limit, ip, skip, dup_scratch, lane, ip_m, batch_ok);
+                if (m) {
+                    ip = ip_m;
+                    skip += m;
+                    st.invalidate();                             // the table has changed under the window's gather
+                    continue;
+                }
+            }
+            batch_ok = true;
             if (win.ensure(ip, lane)) st.invalidate();
             uint32_t r = ip - win.base;
             if (r >= uni(st.cov_end)) st.template gather<true, true>(table, win, dup_scratch, r, kChunk, lane, n);
