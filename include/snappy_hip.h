@@ -731,6 +731,44 @@ SNAPPY_HIP_API int snappy_hip_sz_decompress_batch(const snappy_hip_raw_item *d_i
                                    void *d_scratch, uint64_t scratch_bytes, void *stream);
 
 /*
+ * snappy_hip_sz_decompress_batch with the chunk chain of every LARGE item walked by many wavefronts: for ONE large .sz file,
+ * where the base call spends nearly all its time on one wavefront reading one chunk header after another.
+ * CONTRACT.  Given the same items, max_chunks and flags as snappy_hip_sz_decompress_batch, the following are identical: for every
+ * item d_status[i], d_out_len[i] and d_bad_chunk[i]; d_result[0] and d_result[1]; every byte of dst the base call defines.
+ * Nothing outside [dst, dst + dst_capacity) is written.  A sizing call (capacities of 0) takes the parallel walk too.
+ * How: the compressed bytes are cut into segments.  Segment 0 starts at offset 0; every other segment scans its share for the
+ * first position that looks like a chunk start -- a type 0x00, 0x01 or 0xff header whose length and first bytes are plausible and
+ * from which four more such chunks follow (or the stream ends); skippable types are never taken -- its ANCHOR.  A wavefront per
+ * anchored segment applies the base call's per-chunk tests from its anchor until it lands exactly on a later segment's anchor,
+ * reaches src_len, or meets a chunk the base call refuses.  A join follows these links from segment 0: the item is PROVEN iff
+ * the path reaches src_len with no refusal on it.  The path's chunks are then exactly the chunks the base call's walk visits; a
+ * wrongly guessed anchor is never landed on by the true chain, so it costs time and never an answer, and every large item with
+ * a valid chain inside max_segments is proven.  Every other item -- not large, beyond max_segments, or not proven -- is walked by
+ * one wavefront as in the base call, whose verdict is therefore the answer for every invalid chain.  The decode and the CRC
+ * comparison are the base call's (csrc/snappy_sz_split.hpp).
+ *   segment_bytes  compressed bytes per segment; 0 = the default, 1 MiB.  A multiple of 64, at least 256.
+ *   max_segments   what the scratch has room for: the segments (ceil(src_len / segment_bytes)) of the large items are counted
+ *                  in item order; an item whose segments lie beyond the limit, and every large item behind it, is walked
+ *                  serially.  That is not an error.
+ * An item is LARGE when src_len > segment_bytes.
+ * d_result, 4 words, always written by an accepted call: [0] and [1] as in snappy_hip_sz_decompress_batch, [2] large items whose
+ * chain the parallel walk proved, [3] large items walked serially (beyond max_segments, or not proven).  Items that are not
+ * large, or settled before any walk (a null src, src_len above SNAPPY_HIP_RAW_MAX_LEN), are in neither.
+ * d_scratch: 256-byte aligned device workspace of at least snappy_hip_sz_decompress_split_scratch_bytes(...) bytes (0 for a bad
+ * segment_bytes), not shared with a launch that runs concurrently; contents need not be initialised.  It holds the base call's
+ * scratch, a u64 and a u32 per item and 40 bytes per segment.
+ * The call only enqueues work on `stream` (eight kernels, none of which waits on another workgroup); it never synchronises and
+ * never calls the allocator.  count == 0 is OK.  SNAPPY_HIP_ERR_ARG (host side, nothing enqueued): a bad segment_bytes, an
+ * unknown flag, null arrays with count > 0, a null d_result, a scratch that is misaligned or too small.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_sz_decompress_split_scratch_bytes(uint32_t count, uint32_t max_chunks, uint32_t segment_bytes,
+                                                      uint64_t max_segments);
+SNAPPY_HIP_API int snappy_hip_sz_decompress_split_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t max_chunks,
+                                         uint32_t segment_bytes, uint64_t max_segments, uint32_t flags, uint64_t *d_out_len,
+                                         uint32_t *d_status, uint32_t *d_bad_chunk, uint32_t *d_result, void *d_scratch,
+                                         uint64_t scratch_bytes, void *stream);
+
+/*
  * Item i's src[0, src_len) is plaintext; its output is the 10-byte stream identifier and one chunk per chunk_len (1..65535, K1's
  * block limits) bytes of it, in order.  With R = varint32(n) + the elements K1 produces for the chunk's n bytes as one block
  * (what snappy_hip_raw_compress_batch writes for those bytes alone), the chunk is of type 0x00 and carries R iff R is shorter
@@ -851,6 +889,13 @@ SNAPPY_HIP_API snappy_status snappy_compress_sz_gpu(struct host_buffer_context *
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_sz_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                        uint32_t flags, struct program_runtime *runtime);
+
+/*
+ * snappy_decompress_sz_gpu through snappy_hip_sz_decompress_split_batch (1a'): the same file, the same output, the same
+ * statuses, the chunk chain of a large file walked by many wavefronts at the default segment, with a limit sized from the file.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_sz_split_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                             uint32_t flags, struct program_runtime *runtime);
 
 /* ---- 1d. drop-in level: is this file intact? ----------------------------- */
 

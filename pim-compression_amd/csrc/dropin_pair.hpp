@@ -1096,7 +1096,7 @@ struct SzVerdict {             // what one item's call leaves on the device
     uint64_t out_len;
     uint32_t status;
     uint32_t bad_chunk;
-    uint32_t result[2];
+    uint32_t result[4];        // (the split call writes four words)
 };
 
 // The chunk chain of a .sz file by the rules of snappy_hip_sz_decompress_batch, to size the call: the number of data chunks and
@@ -1131,13 +1131,15 @@ inline const char* sz_host_walk(const uint8_t* s, uint64_t len, uint64_t* chunks
 }
 
 // compress = true: plaintext -> .sz at chunk_len; false: .sz -> plaintext, every CRC compared unless flags says not to.
+// split: the decode goes through snappy_hip_sz_decompress_split_batch at its default segment with a limit sized from the file.
 snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t chunk_len, uint32_t flags,
-                          struct program_runtime* runtime)
+                          struct program_runtime* runtime, bool split = false)
 {
     if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
     PhasedCall call(runtime);
     const uint64_t in_len = input->length;
     uint64_t capacity = 0, scratch_bytes = 0, chunks = 0;
+    const uint64_t segments = (in_len >> 20) + 1;                           // (the default segment_bytes)
     if (compress) {
         if (!block_size_ok(chunk_len)) return say(dropin_plan::bad_block_size(chunk_len, ""));
         if (in_len >> 32) {
@@ -1156,7 +1158,8 @@ snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, stru
             fprintf(stderr, "snappy_hip: not a readable .sz stream: %s\n", why);
             return SNAPPY_INVALID_INPUT;
         }
-        scratch_bytes = snappy_hip_sz_decompress_scratch_bytes(1, (uint32_t)chunks);
+        scratch_bytes = split ? snappy_hip_sz_decompress_split_scratch_bytes(1, (uint32_t)chunks, 0, segments)
+                              : snappy_hip_sz_decompress_scratch_bytes(1, (uint32_t)chunks);
         if (snappy_status st = claim_output(output, capacity)) return st;
     }
     place(output, 0);
@@ -1173,6 +1176,9 @@ snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, stru
     if (snappy_status st = call.launch("sz batch", [&] {
             return compress ? snappy_hip_sz_compress_batch(d_item, 1, chunk_len, (uint32_t)chunks, &d_verdict->out_len, &d_verdict->status,
                                                            d_verdict->result, d_scratch, scratch_bytes, nullptr)
+                   : split  ? snappy_hip_sz_decompress_split_batch(d_item, 1, (uint32_t)chunks, 0, segments, flags, &d_verdict->out_len,
+                                                                   &d_verdict->status, &d_verdict->bad_chunk, d_verdict->result, d_scratch,
+                                                                   scratch_bytes, nullptr)
                             : snappy_hip_sz_decompress_batch(d_item, 1, (uint32_t)chunks, flags, &d_verdict->out_len, &d_verdict->status,
                                                              &d_verdict->bad_chunk, d_verdict->result, d_scratch, scratch_bytes, nullptr);
         }))
@@ -1407,6 +1413,12 @@ snappy_status snappy_decompress_sz_gpu(struct host_buffer_context* input, struct
                                        struct program_runtime* runtime)
 {
     return entry_guard([&] { return sz_gpu_body(false, input, output, 0, flags, runtime); });
+}
+
+snappy_status snappy_decompress_sz_split_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t flags,
+                                             struct program_runtime* runtime)
+{
+    return entry_guard([&] { return sz_gpu_body(false, input, output, 0, flags, runtime, true); });
 }
 
 snappy_status snappy_check_gpu(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)

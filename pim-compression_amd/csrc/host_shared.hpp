@@ -63,4 +63,12 @@ int check_k1_knobs();
 bool lds_table_stream_form(uint32_t block_size);
 uint32_t lds_table_resident_waves(uint32_t lds_bytes);
 
+// The steps of snappy_hip_sz_decompress_batch behind its walks, defined in snappy_hip_sz.hip (which owns their kernels) and shared
+// with the split walk of snappy_hip_sz_split.hip.  d_scratch starts with the parts of sz_decode_layout(count, max_chunks).
+// sz_enqueue_plan: sz_plan_kernel over the items' chunk counts.  sz_enqueue_decode_finish: sz_decode_chunks_kernel over the
+// recorded chunks (none with max_chunks == 0), then sz_finish_kernel.  0, or fail(...).
+int sz_enqueue_plan(hipStream_t st, uint32_t count, uint32_t max_chunks, uint32_t* d_status, uint32_t* d_result, void* d_scratch);
+int sz_enqueue_decode_finish(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t flags,
+                             uint32_t* d_status, uint32_t* d_bad_chunk, uint32_t* d_result, void* d_scratch);
+
 }  // namespace snappy_hip_host

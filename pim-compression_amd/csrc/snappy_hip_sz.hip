@@ -66,18 +66,48 @@ int snappy_hip_sz_decompress_batch(const snappy_hip_raw_item* d_items, uint32_t 
     if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_sz_decompress_scratch_bytes)");
     hipStream_t st = (hipStream_t)stream;
     uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
     uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.prefix);
     SzChunk* chunks = reinterpret_cast<SzChunk*>(scratch + l.chunks);
     const auto* items = reinterpret_cast<const RawItem*>(d_items);
     const uint32_t item_grid = std::min(std::max(count, 1u), 4096u);
     if (count) hipLaunchKernelGGL(sz_index_kernel<false>, dim3(item_grid), dim3(64), 0, st, items, count, max_chunks, d_out_len, d_status, prefix, chunks);
-    hipLaunchKernelGGL(sz_plan_kernel, dim3(1), dim3(1024), 0, st, count, max_chunks, d_status, d_result, ctl, prefix);
-    HIP_TRY(hipGetLastError());
+    if (int rc = sz_enqueue_plan(st, count, max_chunks, d_status, d_result, d_scratch)) return rc;
     if (count == 0) return SNAPPY_HIP_OK;
     if (max_chunks) {
         hipLaunchKernelGGL(sz_index_kernel<true>, dim3(item_grid), dim3(64), 0, st, items, count, max_chunks, d_out_len, d_status, prefix, chunks);
         HIP_TRY(hipGetLastError());
+    }
+    return sz_enqueue_decode_finish(st, d_items, count, max_chunks, flags, d_status, d_bad_chunk, d_result, d_scratch);
+}
+
+}  // extern "C"
+
+// (host_shared.hpp.  Defined here, behind the walks' launches, so that the templates are instantiated -- and the kernels emitted --
+// in the order they always were: tools/kernel_asm_diff.py compares the text.)
+namespace snappy_hip_host {
+
+int sz_enqueue_plan(hipStream_t st, uint32_t count, uint32_t max_chunks, uint32_t* d_status, uint32_t* d_result, void* d_scratch)
+{
+    using namespace snappy_hip;
+    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+    const SzDecodeLayout l = sz_decode_layout(count, max_chunks);
+    hipLaunchKernelGGL(sz_plan_kernel, dim3(1), dim3(1024), 0, st, count, max_chunks, d_status, d_result, reinterpret_cast<uint32_t*>(scratch),
+                       reinterpret_cast<uint64_t*>(scratch + l.prefix));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sz_enqueue_decode_finish(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t flags,
+                             uint32_t* d_status, uint32_t* d_bad_chunk, uint32_t* d_result, void* d_scratch)
+{
+    using namespace snappy_hip;
+    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
+    const SzDecodeLayout l = sz_decode_layout(count, max_chunks);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
+    uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.prefix);
+    SzChunk* chunks = reinterpret_cast<SzChunk*>(scratch + l.chunks);
+    const auto* items = reinterpret_cast<const RawItem*>(d_items);
+    if (max_chunks) {
         const int rc = launch_counted(st, [&](uint32_t* counter) {
             const uint32_t grid = std::min(range_grid_cap(), max_chunks);
             if (crc_tables() == 4) hipLaunchKernelGGL(sz_decode_chunks_kernel<4>, dim3(grid), dim3(64), 0, st, items, ctl, chunks, flags, counter);
@@ -86,10 +116,15 @@ int snappy_hip_sz_decompress_batch(const snappy_hip_raw_item* d_items, uint32_t 
         });
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(sz_finish_kernel, dim3(item_grid), dim3(64), 0, st, count, prefix, chunks, d_status, d_bad_chunk, d_result);
+    hipLaunchKernelGGL(sz_finish_kernel, dim3(std::min(std::max(count, 1u), 4096u)), dim3(64), 0, st, count, prefix, chunks, d_status, d_bad_chunk,
+                       d_result);
     HIP_TRY(hipGetLastError());
-    return SNAPPY_HIP_OK;
+    return 0;
 }
+
+}  // namespace snappy_hip_host
+
+extern "C" {
 
 uint64_t snappy_hip_sz_compress_bound(uint64_t src_len, uint32_t chunk_len)
 {

@@ -140,6 +140,10 @@ __device__ __forceinline__ uint32_t sz_walk(const uint8_t* src, uint64_t src_len
     return st;
 }
 
+// SNAPPY_SZ_NO_KERNELS: a second source of the library that needs SzChunk, sz_walk and the layout (snappy_hip_sz_split.hip, the
+// split walk of snappy_sz_split.hpp) takes this header without its kernels: two of them are no templates and would be defined twice.
+#ifndef SNAPPY_SZ_NO_KERNELS
+
 // One wavefront per item.  kRecord = false: status[i], out_len[i] (the total length whenever the chain parses) and prefix[i] =
 // the item's number of data chunks (0 unless it is OK).  kRecord = true, behind sz_plan_kernel: the chunks of the items still
 // OK are recorded at chunks[prefix[i]..].  Item 0's first chunk is chunk 0 of the batch whatever the plan finds, so the first
@@ -472,5 +476,7 @@ __global__ __launch_bounds__(256) void sz_gather_kernel(const RawItem* __restric
         else workgroup_copy(dst + 8, src + start, n);
     }
 }
+
+#endif  // SNAPPY_SZ_NO_KERNELS
 
 }  // namespace snappy_hip

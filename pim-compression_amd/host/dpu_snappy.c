@@ -7,8 +7,8 @@
  *
  *   dpu_snappy [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]
  *   dpu_snappy [-d] [-R [-S]] -T -i <input_file>
- *   dpu_snappy [-d] [-c] -z [-b <chunk_len>] -i <input_file> [-o <output_file>]
- *   dpu_snappy [-d] -z -T -i <input_file>
+ *   dpu_snappy [-d] [-c] -z [-S] [-b <chunk_len>] -i <input_file> [-o <output_file>]
+ *   dpu_snappy [-d] -z [-S] -T -i <input_file>
  */
 #include <getopt.h>
 #include <limits.h>
@@ -27,13 +27,13 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
 	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] [-R [-S]] -T -i <input_file>\n", exe);
-	fprintf(stderr, "       %s [-d] [-c] -z [-b <chunk_len>] -i <input_file> [-o <output_file>]\n", exe);
-	fprintf(stderr, "       %s [-d] -z -T -i <input_file>\n", exe);
+	fprintf(stderr, "       %s [-d] [-c] -z [-S] [-b <chunk_len>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "       %s [-d] -z [-S] -T -i <input_file>\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
 	fprintf(stderr, "z: the Snappy framing format (.sz, what snzip and the stream classes of other Snappy libraries write): chunks of <block_size> bytes, each with the CRC-32C of its plain bytes, which decompression compares; with -T: decode the file, compare every CRC, write nothing\n");
-	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S; with -d -R -T (no <unit_len>): check one large raw stream with many wavefronts, whatever built it\n");
+	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S; with -d -R -T (no <unit_len>): check one large raw stream with many wavefronts, whatever built it; with -d -z (no <unit_len>), decompressing or with -T: walk the chunk chain of one large .sz stream with many wavefronts\n");
 	fprintf(stderr, "W: with -d, decompressing a block-framed file: put a workgroup of <waves> wavefronts (2, 4, 8 or 16, default 16) on every block instead of one wavefront; for small files\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
@@ -224,12 +224,16 @@ int main(int argc, char **argv)
 		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
 		return -2;
 	}
-	if (sz && (raw || use_range || use_write || use_split || use_wide || use_keep || tail_path)) {
-		fprintf(stderr, "-z reads and writes one .sz stream: it goes with -c, -b, -d and -T only\n");
+	if (sz && (raw || use_range || use_write || use_wide || use_keep || tail_path)) {
+		fprintf(stderr, "-z reads and writes one .sz stream: it goes with -c, -b, -d, -S and -T only\n");
 		return -2;
 	}
-	if (use_split && (!raw || compress)) {
-		fprintf(stderr, "-S splits the decoding or the check (-T) of one raw Snappy stream: it goes with -R and not with -c\n");
+	if (sz && use_split && split_has_unit) {
+		fprintf(stderr, "-S takes no <unit_len> with -z: the chunks of a .sz stream are its units\n");
+		return -2;
+	}
+	if (use_split && ((!raw && !sz) || compress)) {
+		fprintf(stderr, "-S splits the decoding or the check (-T) of one raw Snappy or .sz stream: it goes with -R or -z and not with -c\n");
 		return -2;
 	}
 	if (use_split && use_check && split_has_unit) {
@@ -280,8 +284,8 @@ int main(int argc, char **argv)
 		output.curr = NULL;
 		output.max = ULONG_MAX;
 		if (use_gpu) {
-			st = snappy_decompress_sz_gpu(&input, &output, 0, &rt);
-		} else {
+			st = use_split ? snappy_decompress_sz_split_gpu(&input, &output, 0, &rt) : snappy_decompress_sz_gpu(&input, &output, 0, &rt);
+		} else {                         /* (host mode ignores -S) */
 			gettimeofday(&t0, NULL);
 			st = snappy_decompress_sz_host(&input, &output, 0);
 			gettimeofday(&t1, NULL);
@@ -346,7 +350,9 @@ int main(int argc, char **argv)
 		output.curr = NULL;
 		output.max = ULONG_MAX;
 		if (use_gpu) {
-			st = compress ? snappy_compress_sz_gpu(&input, &output, (uint32_t)block_size, &rt) : snappy_decompress_sz_gpu(&input, &output, 0, &rt);
+			st = compress    ? snappy_compress_sz_gpu(&input, &output, (uint32_t)block_size, &rt)
+			     : use_split ? snappy_decompress_sz_split_gpu(&input, &output, 0, &rt)
+			                 : snappy_decompress_sz_gpu(&input, &output, 0, &rt);   /* (host mode ignores -S) */
 		} else {
 			gettimeofday(&t0, NULL);
 			st = compress ? snappy_compress_sz_host(&input, &output, (uint32_t)block_size) : snappy_decompress_sz_host(&input, &output, 0);

@@ -142,6 +142,10 @@ def lib():
         L.snappy_hip_sz_decompress_scratch_bytes.argtypes = [u32, u32]
         L.snappy_hip_sz_decompress_batch.restype = ctypes.c_int
         L.snappy_hip_sz_decompress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_sz_decompress_split_scratch_bytes.restype = u64
+        L.snappy_hip_sz_decompress_split_scratch_bytes.argtypes = [u32, u32, u32, u64]
+        L.snappy_hip_sz_decompress_split_batch.restype = ctypes.c_int
+        L.snappy_hip_sz_decompress_split_batch.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, u64, vp]
         L.snappy_hip_sz_compress_bound.restype = u64
         L.snappy_hip_sz_compress_bound.argtypes = [u64, u32]
         L.snappy_hip_sz_compress_scratch_bytes.restype = u64
@@ -154,6 +158,9 @@ def lib():
         L.snappy_decompress_sz_gpu.restype = ctypes.c_int
         L.snappy_decompress_sz_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
                                                ctypes.POINTER(ProgramRuntime)]
+        L.snappy_decompress_sz_split_gpu.restype = ctypes.c_int
+        L.snappy_decompress_sz_split_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                                     ctypes.POINTER(ProgramRuntime)]
         L.snappy_hip_check_scratch_bytes.restype = u64
         L.snappy_hip_check_scratch_bytes.argtypes = [u32]
         L.snappy_hip_check_blocks.restype = ctypes.c_int
@@ -641,6 +648,29 @@ def sz_decompress_batch(d_items, count, max_chunks, d_out_len, d_status, d_bad_c
     return d_scratch
 
 
+def sz_decompress_split_scratch_bytes(count, max_chunks, segment_bytes, max_segments):
+    """Scratch of snappy_hip_sz_decompress_split_batch (0 for a bad segment_bytes)."""
+    return int(lib().snappy_hip_sz_decompress_split_scratch_bytes(count, max_chunks, segment_bytes, max_segments))
+
+
+def sz_decompress_split_batch(d_items, count, max_chunks, segment_bytes, max_segments, d_out_len, d_status, d_bad_chunk, d_result, flags=0,
+                              d_scratch=None):
+    """Enqueue snappy_hip_sz_decompress_split_batch on the current stream: sz_decompress_batch with the chunk chain of every item
+    of more than one segment walked by many wavefronts; the same answers.  segment_bytes: 0 = the default (1 MiB); max_segments:
+    what the scratch is sized for.  d_result: device int32 tensor of four (chunks the batch needs, items OK, large items the
+    parallel walk proved, large items walked serially).  d_scratch: 256-byte aligned device uint8 tensor (default: a fresh one).
+    Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(sz_decompress_split_scratch_bytes(count, max_chunks, segment_bytes, max_segments), 256), dtype=torch.uint8,
+                                device=d_result.device)
+    _check(lib().snappy_hip_sz_decompress_split_batch(d_items.data_ptr() if count else None, count, max_chunks, segment_bytes, max_segments, flags,
+                                                      d_out_len.data_ptr() if count else None, d_status.data_ptr() if count else None,
+                                                      d_bad_chunk.data_ptr() if count else None, d_result.data_ptr(), d_scratch.data_ptr(),
+                                                      d_scratch.numel(), _stream_handle(torch)), "snappy_hip_sz_decompress_split_batch")
+    return d_scratch
+
+
 def sz_compress_bound(src_len, chunk_len):
     """10 + 8 * chunks + src_len: a dst_capacity that always suffices, exact when nothing compresses (0 for a bad chunk_len)."""
     return int(lib().snappy_hip_sz_compress_bound(src_len, chunk_len))
@@ -909,6 +939,11 @@ def sz_compress_host(data, chunk_len=32768, out_capacity=None):
 def sz_decompress_host(stream, flags=0, out_capacity=None):
     """snappy_decompress_sz_gpu on a whole .sz stream held in host memory -> (status, plaintext, runtime dict)."""
     return _raw_host(lambda i, o, r: lib().snappy_decompress_sz_gpu(i, o, flags, r), stream, out_capacity)
+
+
+def sz_decompress_split_host(stream, flags=0, out_capacity=None):
+    """snappy_decompress_sz_split_gpu on a whole .sz stream held in host memory -> (status, plaintext, runtime dict)."""
+    return _raw_host(lambda i, o, r: lib().snappy_decompress_sz_split_gpu(i, o, flags, r), stream, out_capacity)
 
 
 def check_host(stream):
