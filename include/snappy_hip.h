@@ -784,6 +784,79 @@ SNAPPY_HIP_API int snappy_hip_sz_compress_batch(const snappy_hip_raw_item *d_ite
                                  uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result, void *d_scratch,
                                  uint64_t scratch_bytes, void *stream);
 
+/* ---- 1a''. byte ranges of .sz streams from a resident chunk index -------- */
+
+/*
+ * The data chunks of a .sz stream are as independent as a container's blocks: each holds at most 65,536 bytes of plaintext behind a
+ * CRC-32C of its own.  snappy_hip_sz_index_batch walks the chains once and leaves an INDEX in the caller's memory -- one
+ * snappy_hip_sz_chunk per data chunk, one snappy_hip_sz_desc per stream -- and snappy_hip_sz_decompress_ranges decodes byte ranges
+ * of the plaintext from it, touching only the chunks the ranges touch (csrc/snappy_sz_ranges.hpp).
+ */
+typedef struct snappy_hip_sz_chunk {   /* 32 bytes: one DATA chunk of a stream */
+    uint64_t src_off;   /* of the chunk's type byte in the stream                         */
+    uint64_t dst_off;   /* of its first plaintext byte in the stream's plaintext           */
+    uint32_t info;      /* L | bytes of the varint << 24 | (type 0x00) << 28               */
+    uint32_t ulen;      /* uncompressed length, <= 65,536                                  */
+    uint32_t item;      /* the item of the index call                                      */
+    uint32_t reserved;  /* 0 */
+} snappy_hip_sz_chunk;
+
+typedef struct snappy_hip_sz_desc {    /* 40 bytes: one indexed stream */
+    const uint8_t *src; uint64_t src_len;
+    const snappy_hip_sz_chunk *chunks; uint64_t num_chunks;
+    uint64_t total_len;
+} snappy_hip_sz_desc;
+
+/*
+ * The index of `count` .sz streams.  The items are snappy_hip_raw_item; their dst and dst_capacity are IGNORED.  Every chain is
+ * walked exactly as snappy_hip_sz_decompress_split_batch walks it (the parallel walk for items of more than segment_bytes, the
+ * serial walk for the rest, the same segment_bytes / max_segments rules).  The records of all items go to d_chunks[0, max_chunks)
+ * in item order; d_descs[i] = { src, src_len, d_chunks + the first chunk of item i, num_chunks, total_len }.
+ * d_status[i]: what the decode call answers with unlimited capacity before any chunk is decoded -- SNAPPY_HIP_BLOCK_OK,
+ * SNAPPY_HIP_BLOCK_INVALID, SNAPPY_HIP_SZ_UNSUPPORTED or SNAPPY_HIP_RAW_TOO_LARGE, never SNAPPY_HIP_RAW_DST_TOO_SMALL.  An item
+ * that is not OK gets num_chunks = 0 and total_len = 0: no range can touch it.
+ * d_result: 4 words with the split call's meanings; [1] counts the items indexed OK.
+ * d_scratch: 256-byte aligned, at least snappy_hip_sz_index_scratch_bytes(...) bytes (0 for a bad segment_bytes): the split call's
+ * scratch, a shadow item and a u64 per item.  The call only enqueues work on `stream` and never calls the allocator.
+ * SNAPPY_HIP_ERR_ARG (host side, nothing enqueued): the split call's cases.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_sz_index_scratch_bytes(uint32_t count, uint32_t max_chunks, uint32_t segment_bytes, uint64_t max_segments);
+SNAPPY_HIP_API int snappy_hip_sz_index_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t max_chunks, uint32_t segment_bytes,
+                              uint64_t max_segments, snappy_hip_sz_chunk *d_chunks, snappy_hip_sz_desc *d_descs, uint32_t *d_status,
+                              uint32_t *d_result, void *d_scratch, uint64_t scratch_bytes, void *stream);
+
+/*
+ * Range r asks for plaintext bytes [offset, offset + length) of the stream d_descs[stream] and gets them at dst.  Its PIECES are
+ * the data chunks first..last of that stream: first = the largest k with dst_off[k] <= offset, last = the largest k with
+ * dst_off[k] <= offset + length - 1; empty chunks between them are pieces too.  A piece wholly inside the range is decoded in
+ * place, the first and last piece -- when only part of them is wanted -- into a 65,536-byte slot of d_scratch, from which the
+ * wanted bytes are copied.  Unless flags has SNAPPY_HIP_SZ_NO_VERIFY the CRC-32C of every piece is compared, over the whole chunk.
+ * d_status[r], always written:
+ *   SNAPPY_HIP_BLOCK_OK             every touched chunk decodes to its stated length and holds its CRC;
+ *   SNAPPY_HIP_BLOCK_INVALID or
+ *   SNAPPY_HIP_SZ_CRC_MISMATCH      the status of the LOWEST-NUMBERED bad chunk the range touches; d_bad_chunk[r] is its number in
+ *                                   its stream.  The contents of dst are then unspecified but confined to the range;
+ *   SNAPPY_HIP_RANGE_OUT_OF_BOUNDS  stream >= count, offset + length > total_len or overflowing, a null dst with length > 0, a desc
+ *                                   whose records hold no chunk at the range's start, or pieces beyond the 2^31st of the call.
+ *                                   Nothing is written to dst.
+ * d_bad_chunk[r] is 0xffffffff unless a chunk is named.  A chunk the range does not touch never influences the answer.  A range
+ * of length 0 is OK and writes nothing.
+ * The index is the caller's memory and may be stale, and the streams are not trusted either: before a piece is decoded its record
+ * is held to the desc and the stream (src_off + 4 + L <= src_len, L >= 4 + varint bytes, ulen <= 65,536, the header re-read at
+ * src_off has the record's type and L, the varint re-read there states ulen); a record that fails is BLOCK_INVALID for that piece.
+ * Whatever records and streams hold, nothing outside [src, src + src_len) is read (the num_chunks records excepted) and nothing
+ * outside [dst, dst + length) of a range is written (the slots excepted).
+ * d_scratch: 256-byte aligned; the piece prefix (range_count + 2 u64), two u64 per range, each part rounded up to 256 bytes, then
+ * one slot per wavefront.  The grid is the persistent kernels' or the slots the scratch holds, whichever is smaller; room for one
+ * slot is valid, less is SNAPPY_HIP_ERR_ARG.  snappy_hip_sz_decompress_ranges_scratch_bytes returns the size for the full grid.
+ * The call only enqueues work on `stream`.  SNAPPY_HIP_ERR_ARG (host side, nothing enqueued): an unknown flag, null arrays with
+ * range_count > 0, a scratch that is misaligned or too small.
+ */
+SNAPPY_HIP_API uint64_t snappy_hip_sz_decompress_ranges_scratch_bytes(uint32_t range_count);
+SNAPPY_HIP_API int snappy_hip_sz_decompress_ranges(const snappy_hip_sz_desc *d_descs, uint32_t count, const snappy_hip_range *d_ranges,
+                                    uint32_t range_count, uint32_t flags, uint32_t *d_status, uint32_t *d_bad_chunk, void *d_scratch,
+                                    uint64_t scratch_bytes, void *stream);
+
 /* ---- 1b. drop-in level: one byte range of a framed file ----------------- */
 
 /*
@@ -896,6 +969,17 @@ SNAPPY_HIP_API snappy_status snappy_decompress_sz_gpu(struct host_buffer_context
  */
 SNAPPY_HIP_API snappy_status snappy_decompress_sz_split_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                              uint32_t flags, struct program_runtime *runtime);
+
+/*
+ * Bytes [offset, offset + length) of the plaintext of the .sz stream in input (the whole file).  The host walks the chunk chain
+ * only up to the last chunk the range touches and copies only the touched chunks' bytes and their records (rebased to the copied
+ * span) to the device; one range goes through snappy_hip_sz_decompress_ranges (1a'').  output as in snappy_decompress_range_gpu.
+ * flags: SNAPPY_HIP_SZ_NO_VERIFY.  SNAPPY_INVALID_INPUT: a chain broken before the range ends, a range beyond the plaintext, or
+ * a touched chunk that does not decode or fails its CRC-32C (named on stderr by its number among the stream's data chunks); a
+ * chunk the range does not touch is never read.  Fills every field of *runtime.
+ */
+SNAPPY_HIP_API snappy_status snappy_decompress_sz_range_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                             uint64_t offset, uint64_t length, uint32_t flags, struct program_runtime *runtime);
 
 /* ---- 1d. drop-in level: is this file intact? ----------------------------- */
 

@@ -1206,6 +1206,108 @@ snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, stru
     return SNAPPY_OK;
 }
 
+// One byte range of a .sz file's plaintext (snappy_decompress_sz_range_gpu): the chunk chain on the host only up to the last chunk
+// the range touches (sz_host_walk's tests, chunk by chunk), only the touched chunks' bytes and their records -- rebased to the
+// copied span -- to the device, one range through snappy_hip_sz_decompress_ranges, `length` bytes back.
+snappy_status sz_range_gpu_body(struct host_buffer_context* input, struct host_buffer_context* output, uint64_t offset, uint64_t length,
+                                uint32_t flags, struct program_runtime* runtime)
+{
+    if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
+    if (flags & ~SNAPPY_HIP_SZ_NO_VERIFY) return SNAPPY_INVALID_INPUT;
+    PhasedCall call(runtime);
+    const uint8_t* const s = input->buffer;
+    const uint64_t len = input->length, end = offset + length;
+    const char* why = end < offset ? "the range overflows" : len > SNAPPY_HIP_RAW_MAX_LEN ? "the file is longer than SNAPPY_HIP_RAW_MAX_LEN" : nullptr;
+    std::vector<snappy_hip_sz_chunk> recs;      // the touched chunks: dst_off + ulen > offset and dst_off < end (the device's first..last)
+    uint64_t at = 0, total = 0, first_k = 0, k = 0;
+    bool identified = false;
+    while (!why && at < len && !(identified && total >= end)) {
+        if (at + 4 > len) why = "a chunk header runs past the end of the file";
+        if (why) break;
+        const uint32_t type = s[at], L = s[at + 1] | (uint32_t)s[at + 2] << 8 | (uint32_t)s[at + 3] << 16;
+        if (at + 4 + L > len) {
+            why = "a chunk runs past the end of the file";
+        } else if (type == 0xffu) {
+            if (L != 6 || memcmp(s + at + 4, "sNaPpY", 6) != 0) why = "a wrong stream identifier";
+            identified = true;
+        } else if (!identified) {
+            why = "the first chunk is not the stream identifier";
+        } else if (type <= 1u) {
+            uint32_t n = L - 4, hdr = 0;
+            if (L < 4) why = "a data chunk without room for its checksum";
+            else if (type == 0 && !(hdr = get_varint32(s + at + 8, L - 4, &n))) why = "a compressed chunk without a readable length";
+            else if (n > 65536u) why = "a chunk of more than 65536 bytes";
+            if (why) break;
+            if (length && total < end && total + n > offset) {
+                if (recs.empty()) first_k = k;
+                recs.push_back(snappy_hip_sz_chunk{at, total, L | (hdr << 24) | (type == 0 ? 1u << 28 : 0u), n, 0, 0});
+            }
+            total += n;
+            ++k;
+        } else if (type < 0x80u) {
+            why = "a reserved unskippable chunk";
+        }
+        at += 4ull + L;
+    }
+    if (!why && !identified) why = "no stream identifier";
+    if (why) {
+        (void)call.done_on_host();
+        fprintf(stderr, "snappy_hip: not a readable .sz stream in front of the range's end: %s\n", why);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (total < end) {
+        (void)call.done_on_host();
+        fprintf(stderr, "snappy_hip: the range [%lu, %lu) lies beyond the plaintext of %lu bytes\n", (unsigned long)offset, (unsigned long)end,
+                (unsigned long)total);
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (snappy_status st = claim_output(output, length)) return st;
+    place(output, 0);
+    if (length == 0) return call.done_on_host();
+    const uint64_t in_lo = recs.front().src_off, in_len = recs.back().src_off + 4 + (recs.back().info & 0xffffffu) - in_lo;
+    for (snappy_hip_sz_chunk& r : recs) r.src_off -= in_lo;
+    if (snappy_status st = call.need_device()) return st;
+    const uint64_t cap = range_grid_cap();
+    const uint64_t scratch_bytes = snappy_hip_sz_decompress_ranges_scratch_bytes(1) - cap * 65536u + std::min<uint64_t>(recs.size(), cap) * 65536u;
+
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    snappy_hip_sz_chunk* d_chunks = nullptr;
+    snappy_hip_sz_desc* d_desc = nullptr;
+    snappy_hip_range* d_range = nullptr;
+    uint32_t* d_words = nullptr;                // [0] the range's status, [1] its bad chunk
+    if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_chunks, recs.size() * sizeof(snappy_hip_sz_chunk)}, {&d_desc, sizeof *d_desc},
+                                         {&d_range, sizeof *d_range}, {&d_words, 2 * sizeof(uint32_t)}, {&d_out, length}, {&d_scratch, scratch_bytes}}))
+        return st;
+    const snappy_hip_sz_desc desc{d_in, in_len, d_chunks, recs.size(), total};
+    const snappy_hip_range range{offset, length, d_out, 0, 0};
+    if (snappy_status st = call.upload({{d_in, s + in_lo, in_len}, {d_chunks, recs.data(), recs.size() * sizeof(snappy_hip_sz_chunk)},
+                                        {d_desc, &desc, sizeof desc}, {d_range, &range, sizeof range}}))
+        return st;
+    if (snappy_status st = call.launch("sz range decode", [&] {
+            return snappy_hip_sz_decompress_ranges(d_desc, 1, d_range, 1, flags, d_words, d_words + 1, d_scratch, scratch_bytes, nullptr);
+        }))
+        return st;
+    uint32_t words[2] = {0xffffffffu, 0xffffffffu};
+    if (snappy_status st = call.copy_out([&]() -> int {
+            if (int rc = call.download({{words, d_words, sizeof words}})) return rc;
+            return words[0] == SNAPPY_HIP_BLOCK_OK ? call.download({{output->buffer, d_out, length}}) : 0;
+        }))
+        return st;
+    if (snappy_status st = call.free_buffers()) return st;
+    if (words[0] == SNAPPY_HIP_SZ_CRC_MISMATCH || words[0] == SNAPPY_HIP_BLOCK_INVALID) {
+        fprintf(stderr, "snappy_hip: data chunk %lu of the .sz stream %s\n", (unsigned long)(first_k + words[1]),
+                words[0] == SNAPPY_HIP_SZ_CRC_MISMATCH ? "fails its CRC-32C" : "does not decode");
+        return SNAPPY_INVALID_INPUT;
+    }
+    if (words[0] != SNAPPY_HIP_BLOCK_OK) {
+        fprintf(stderr, "snappy_hip: the range [%lu, %lu) of the .sz stream cannot be decoded (status %u)\n", (unsigned long)offset, (unsigned long)end,
+                words[0]);
+        return SNAPPY_INVALID_INPUT;
+    }
+    place(output, length);
+    return SNAPPY_OK;
+}
+
 // Is a framed file intact (snappy_check_gpu)?  The header and the whole size chain on the host, the whole stream to the device,
 // one snappy_hip_check_blocks, 16 bytes back.  A broken header or chain is decided here: nothing is sent to the device.
 snappy_status check_gpu_body(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)
@@ -1419,6 +1521,12 @@ snappy_status snappy_decompress_sz_split_gpu(struct host_buffer_context* input, 
                                              struct program_runtime* runtime)
 {
     return entry_guard([&] { return sz_gpu_body(false, input, output, 0, flags, runtime, true); });
+}
+
+snappy_status snappy_decompress_sz_range_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint64_t offset,
+                                             uint64_t length, uint32_t flags, struct program_runtime* runtime)
+{
+    return entry_guard([&] { return sz_range_gpu_body(input, output, offset, length, flags, runtime); });
 }
 
 snappy_status snappy_check_gpu(struct host_buffer_context* input, snappy_hip_check_report* report, struct program_runtime* runtime)

@@ -71,4 +71,14 @@ int sz_enqueue_plan(hipStream_t st, uint32_t count, uint32_t max_chunks, uint32_
 int sz_enqueue_decode_finish(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t flags,
                              uint32_t* d_status, uint32_t* d_bad_chunk, uint32_t* d_result, void* d_scratch);
 
+// Steps 1 to 6 of snappy_hip_sz_decompress_split_batch (snappy_sz_split.hpp: plan, anchors, walkers, join, sz_enqueue_plan, record),
+// defined in snappy_hip_sz_split.hip (which owns their kernels) and shared with the index call of snappy_hip_sz_ranges.hip.
+// The arguments are validated by the caller: segment_bytes is a good one (not 0), max_segments at most 2^31, d_scratch holds
+// sz_split_layout(count, max_chunks, max_segments).  0, or fail(...).
+int sz_split_enqueue_walk(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t segment_bytes,
+                          uint64_t max_segments, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch);
+// segment_bytes 0 becomes the default; whether it is a good one.  The split walk's scratch (sz_split_layout's total).
+bool sz_split_segment_ok(uint32_t& segment_bytes);
+uint64_t sz_split_scratch_total(uint32_t count, uint32_t max_chunks, uint64_t max_segments);
+
 }  // namespace snappy_hip_host

@@ -26,28 +26,20 @@ static bool sz_split_params(uint32_t& segment_bytes)
     return segment_bytes >= snappy_hip::kSzSplitMinSegment && segment_bytes % 64u == 0;
 }
 
-extern "C" {
+namespace snappy_hip_host {
 
-uint64_t snappy_hip_sz_decompress_split_scratch_bytes(uint32_t count, uint32_t max_chunks, uint32_t segment_bytes, uint64_t max_segments)
+bool sz_split_segment_ok(uint32_t& segment_bytes) { return sz_split_params(segment_bytes); }
+
+uint64_t sz_split_scratch_total(uint32_t count, uint32_t max_chunks, uint64_t max_segments)
 {
-    if (!sz_split_params(segment_bytes)) return 0;
     return snappy_hip::sz_split_layout(count, max_chunks, max_segments).total;
 }
 
-int snappy_hip_sz_decompress_split_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t segment_bytes,
-                                         uint64_t max_segments, uint32_t flags, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_bad_chunk,
-                                         uint32_t* d_result, void* d_scratch, uint64_t scratch_bytes, void* stream)
+int sz_split_enqueue_walk(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t segment_bytes,
+                          uint64_t max_segments, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch)
 {
     using namespace snappy_hip;
-    static_assert(sizeof(snappy_hip_raw_item) == sizeof(RawItem), "snappy_hip_raw_item layout");
-    if (!sz_split_params(segment_bytes)) return fail(SNAPPY_HIP_ERR_ARG, "segment_bytes must be 0 or a multiple of 64 of at least 256");
-    if (flags & ~SNAPPY_HIP_SZ_NO_VERIFY) return fail(SNAPPY_HIP_ERR_ARG, "unknown flag (SNAPPY_HIP_SZ_NO_VERIFY is the only one)");
-    if (!d_result || (count && (!d_items || !d_out_len || !d_status || !d_bad_chunk))) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
-    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
-    max_segments = std::min(max_segments, kSzSplitMaxSegments);
     const SzSplitLayout l = sz_split_layout(count, max_chunks, max_segments);
-    if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_sz_decompress_split_scratch_bytes)");
-    hipStream_t st = (hipStream_t)stream;
     uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
     uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
     uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.d.prefix);
@@ -73,13 +65,42 @@ int snappy_hip_sz_decompress_split_batch(const snappy_hip_raw_item* d_items, uin
         HIP_TRY(hipGetLastError());
     }
     if (int rc = sz_enqueue_plan(st, count, max_chunks, d_status, d_result, d_scratch)) return rc;
-    if (count == 0) return SNAPPY_HIP_OK;
+    if (count == 0) return 0;
     if (max_chunks) {
         const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)seg_grid + item_grid, 65536u);
         hipLaunchKernelGGL(sz_split_record_kernel, dim3(grid), dim3(64), 0, st, items, count, segment_bytes, ctl, d_status, prefix, chunks, seg_prefix,
                            item_flags, segs);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+}  // namespace snappy_hip_host
+
+extern "C" {
+
+uint64_t snappy_hip_sz_decompress_split_scratch_bytes(uint32_t count, uint32_t max_chunks, uint32_t segment_bytes, uint64_t max_segments)
+{
+    if (!sz_split_params(segment_bytes)) return 0;
+    return snappy_hip::sz_split_layout(count, max_chunks, max_segments).total;
+}
+
+int snappy_hip_sz_decompress_split_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t max_chunks, uint32_t segment_bytes,
+                                         uint64_t max_segments, uint32_t flags, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_bad_chunk,
+                                         uint32_t* d_result, void* d_scratch, uint64_t scratch_bytes, void* stream)
+{
+    using namespace snappy_hip;
+    static_assert(sizeof(snappy_hip_raw_item) == sizeof(RawItem), "snappy_hip_raw_item layout");
+    if (!sz_split_params(segment_bytes)) return fail(SNAPPY_HIP_ERR_ARG, "segment_bytes must be 0 or a multiple of 64 of at least 256");
+    if (flags & ~SNAPPY_HIP_SZ_NO_VERIFY) return fail(SNAPPY_HIP_ERR_ARG, "unknown flag (SNAPPY_HIP_SZ_NO_VERIFY is the only one)");
+    if (!d_result || (count && (!d_items || !d_out_len || !d_status || !d_bad_chunk))) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
+    if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
+    max_segments = std::min(max_segments, kSzSplitMaxSegments);
+    const SzSplitLayout l = sz_split_layout(count, max_chunks, max_segments);
+    if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_sz_decompress_split_scratch_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = sz_split_enqueue_walk(st, d_items, count, max_chunks, segment_bytes, max_segments, d_out_len, d_status, d_result, d_scratch)) return rc;
+    if (count == 0) return SNAPPY_HIP_OK;
     return sz_enqueue_decode_finish(st, d_items, count, max_chunks, flags, d_status, d_bad_chunk, d_result, d_scratch);
 }
 

@@ -47,6 +47,9 @@ __device__ __forceinline__ uint64_t range_pieces(const StreamDesc* __restrict__ 
     return last - first + 1;
 }
 
+// (SNAPPY_HIP_NO_KERNELS, snappy_kernels.hpp: another source of the library takes RangeDesc and the pieces above without the kernels)
+#ifndef SNAPPY_HIP_NO_KERNELS
+
 __global__ __launch_bounds__(1024) void range_pieces_kernel(const StreamDesc* __restrict__ descs, uint32_t count,
                                                             const RangeDesc* __restrict__ ranges, uint32_t range_count,
                                                             uint32_t* __restrict__ status, uint32_t max_block_size,
@@ -131,5 +134,7 @@ __global__ __launch_bounds__(64) void decompress_ranges_kernel(const StreamDesc*
         __syncthreads();
     }
 }
+
+#endif  // SNAPPY_HIP_NO_KERNELS
 
 }  // namespace snappy_hip

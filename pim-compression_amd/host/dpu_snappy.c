@@ -9,6 +9,7 @@
  *   dpu_snappy [-d] [-R [-S]] -T -i <input_file>
  *   dpu_snappy [-d] [-c] -z [-S] [-b <chunk_len>] -i <input_file> [-o <output_file>]
  *   dpu_snappy [-d] -z [-S] -T -i <input_file>
+ *   dpu_snappy [-d] -z -x <offset>:<length> -i <input_file> [-o <output_file>]
  */
 #include <getopt.h>
 #include <limits.h>
@@ -29,6 +30,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "       %s [-d] [-R [-S]] -T -i <input_file>\n", exe);
 	fprintf(stderr, "       %s [-d] [-c] -z [-S] [-b <chunk_len>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] -z [-S] -T -i <input_file>\n", exe);
+	fprintf(stderr, "       %s [-d] -z -x <offset>:<length> -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "d: use the GPU(s), by default host is used\n");
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
@@ -38,6 +40,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
 	fprintf(stderr, "g: number of GPUs to shard blocks over with -d, default all visible\n");
 	fprintf(stderr, "r: decompress only <length> bytes from uncompressed byte <offset> of the input\n");
+	fprintf(stderr, "x: with -z: extract only <length> bytes from plaintext byte <offset> of a .sz stream; only the chunks the range touches are read, decoded and held to their CRCs\n");
 	fprintf(stderr, "w: overwrite the uncompressed bytes from <offset> with <patch_file>, recompressing only the touched blocks\n");
 	fprintf(stderr, "t: keep only the first <keep_len> uncompressed bytes of the input (with -a: then append)\n");
 	fprintf(stderr, "a: append <tail_file> to the uncompressed bytes, compressing only the blocks from the cut on; alone it keeps everything\n");
@@ -110,6 +113,8 @@ int main(int argc, char **argv)
 
 	int use_range = 0;
 	unsigned long long range_off = 0, range_len = 0;
+	int use_extract = 0;                                     /* -z -x: a range of a .sz stream's plaintext */
+	unsigned long long extract_off = 0, extract_len = 0;
 	int use_write = 0;
 	unsigned long long write_off = 0;
 	const char *patch_path = NULL;
@@ -124,7 +129,7 @@ int main(int argc, char **argv)
 	int split_has_unit = 0;
 	int use_wide = 0;
 	unsigned long wide_waves = 0;
-	while ((opt = getopt(argc, argv, "dcRzTS::W::b:g:i:o:r:w:t:a:")) != -1) {
+	while ((opt = getopt(argc, argv, "dcRzTS::W::b:g:i:o:r:w:t:a:x:")) != -1) {
 		switch (opt) {
 		case 'S': {                  /* -S, -S<unit_len> or -S <unit_len> */
 			const char *arg = optarg;
@@ -195,6 +200,21 @@ int main(int argc, char **argv)
 			use_range = 1;
 			break;
 		}
+		case 'x': {                  /* extract only bytes [offset, offset + length) of a .sz stream's plaintext */
+			char *colon = NULL, *tail = NULL;
+			extract_off = strtoull(optarg, &colon, 10);
+			if (colon == optarg || *colon != ':' || optarg[0] == '-' || colon[1] == '-' || colon[1] == '\0') {
+				fprintf(stderr, "-x wants <offset>:<length> in bytes, got '%s'\n", optarg);
+				return -2;
+			}
+			extract_len = strtoull(colon + 1, &tail, 10);
+			if (*tail != '\0') {
+				fprintf(stderr, "-x wants <offset>:<length> in bytes, got '%s'\n", optarg);
+				return -2;
+			}
+			use_extract = 1;
+			break;
+		}
 		case 'd': use_gpu = 1; break;
 		case 'c': compress = 1; break;
 		case 'R': raw = 1; break;
@@ -224,8 +244,12 @@ int main(int argc, char **argv)
 		fprintf(stderr, "-R reads and writes one raw Snappy stream: it has no blocks for -r or -w to select\n");
 		return -2;
 	}
+	if (use_extract && (!sz || compress || use_check || raw || use_split || use_wide)) {
+		fprintf(stderr, "-x extracts a byte range of one .sz stream: it goes with -z and not with -c, -T, -R, -S or -W\n");
+		return -2;
+	}
 	if (sz && (raw || use_range || use_write || use_wide || use_keep || tail_path)) {
-		fprintf(stderr, "-z reads and writes one .sz stream: it goes with -c, -b, -d, -S and -T only\n");
+		fprintf(stderr, "-z reads and writes one .sz stream: it goes with -c, -b, -d, -S, -T and -x only\n");
 		return -2;
 	}
 	if (sz && use_split && split_has_unit) {
@@ -344,7 +368,20 @@ int main(int argc, char **argv)
 		printf("Free time: %f\n", rt.d_free);
 		return st == SNAPPY_OK ? 0 : 1;
 	}
-	if (sz) {
+	if (sz && use_extract) {
+		/* only the chunks the range touches are read and decoded; both modes allocate the output */
+		output.buffer = NULL;
+		output.curr = NULL;
+		output.max = ULONG_MAX;
+		if (use_gpu) {
+			st = snappy_decompress_sz_range_gpu(&input, &output, extract_off, extract_len, 0, &rt);
+		} else {
+			gettimeofday(&t0, NULL);
+			st = snappy_decompress_sz_range_host(&input, &output, extract_off, extract_len, 0);
+			gettimeofday(&t1, NULL);
+			rt.run = get_runtime(&t0, &t1);
+		}
+	} else if (sz) {
 		/* one .sz stream, either way; both modes allocate the output */
 		output.buffer = NULL;
 		output.curr = NULL;

@@ -423,55 +423,69 @@ snappy_status snappy_compress_sz_host(struct host_buffer_context *input, struct 
 	return SNAPPY_OK;
 }
 
-/* The chunk chain of a whole .sz file by the rules of snappy_hip_sz_decompress_batch: the sum of the data chunks' uncompressed
- * lengths, or why the stream is refused.  Reads nothing outside [buf, buf + len). */
+/* The chunk at buf + at (at < len) by the rules of snappy_hip_sz_decompress_batch: its type, its L and, for a data chunk, its
+ * uncompressed length n; *identified follows the chain.  Or why the stream is refused.  Reads nothing outside [buf, buf + len). */
+static snappy_status sz_chunk_host(const uint8_t *buf, unsigned long len, unsigned long at, int *identified, uint32_t *type_out,
+                                   uint32_t *L_out, uint32_t *n_out)
+{
+	if (len - at < 4) {
+		fprintf(stderr, "a chunk header runs past the end of the file\n");
+		return SNAPPY_INVALID_INPUT;
+	}
+	const uint32_t type = buf[at], L = buf[at + 1] | (uint32_t)buf[at + 2] << 8 | (uint32_t)buf[at + 3] << 16;
+	if (len - at - 4 < L) {
+		fprintf(stderr, "the chunk at offset %lu runs past the end of the file\n", at);
+		return SNAPPY_INVALID_INPUT;
+	}
+	const uint8_t *body = buf + at + 4;
+	uint32_t n = 0;
+	if (type == 0xff) {
+		if (L != 6 || memcmp(body, "sNaPpY", 6) != 0) {
+			fprintf(stderr, "a wrong stream identifier at offset %lu\n", at);
+			return SNAPPY_INVALID_INPUT;
+		}
+		*identified = 1;
+	} else if (!*identified) {
+		fprintf(stderr, "the first chunk is not the stream identifier\n");
+		return SNAPPY_INVALID_INPUT;
+	} else if (type <= 1) {
+		n = L - 4;
+		if (L < 4) {
+			fprintf(stderr, "the data chunk at offset %lu has no room for its checksum\n", at);
+			return SNAPPY_INVALID_INPUT;
+		}
+		if (type == 0) {
+			const uint8_t *p = varint_get(body + 4, body + L, &n);
+			if (!p || (p - (body + 4) == 5 && p[-1] >= 16)) {
+				fprintf(stderr, "the compressed chunk at offset %lu has no readable length\n", at);
+				return SNAPPY_INVALID_INPUT;
+			}
+		}
+		if (n > 65536) {
+			fprintf(stderr, "the chunk at offset %lu holds more than 65536 bytes\n", at);
+			return SNAPPY_INVALID_INPUT;
+		}
+	} else if (type < 0x80) {
+		fprintf(stderr, "reserved unskippable chunk 0x%02x at offset %lu\n", type, at);
+		return SNAPPY_INVALID_INPUT;
+	}
+	*type_out = type;
+	*L_out = L;
+	*n_out = n;
+	return SNAPPY_OK;
+}
+
+/* The chunk chain of a whole .sz file: the sum of the data chunks' uncompressed lengths, or why the stream is refused. */
 static snappy_status sz_walk_host(const uint8_t *buf, unsigned long len, uint64_t *total)
 {
 	unsigned long at = 0;
 	int identified = 0;
 	*total = 0;
 	while (at < len) {
-		if (len - at < 4) {
-			fprintf(stderr, "a chunk header runs past the end of the file\n");
+		uint32_t type, L, n;
+		if (sz_chunk_host(buf, len, at, &identified, &type, &L, &n) != SNAPPY_OK)
 			return SNAPPY_INVALID_INPUT;
-		}
-		const uint32_t type = buf[at], L = buf[at + 1] | (uint32_t)buf[at + 2] << 8 | (uint32_t)buf[at + 3] << 16;
-		if (len - at - 4 < L) {
-			fprintf(stderr, "the chunk at offset %lu runs past the end of the file\n", at);
-			return SNAPPY_INVALID_INPUT;
-		}
-		const uint8_t *body = buf + at + 4;
-		if (type == 0xff) {
-			if (L != 6 || memcmp(body, "sNaPpY", 6) != 0) {
-				fprintf(stderr, "a wrong stream identifier at offset %lu\n", at);
-				return SNAPPY_INVALID_INPUT;
-			}
-			identified = 1;
-		} else if (!identified) {
-			fprintf(stderr, "the first chunk is not the stream identifier\n");
-			return SNAPPY_INVALID_INPUT;
-		} else if (type <= 1) {
-			uint32_t n = L - 4;
-			if (L < 4) {
-				fprintf(stderr, "the data chunk at offset %lu has no room for its checksum\n", at);
-				return SNAPPY_INVALID_INPUT;
-			}
-			if (type == 0) {
-				const uint8_t *p = varint_get(body + 4, body + L, &n);
-				if (!p || (p - (body + 4) == 5 && p[-1] >= 16)) {
-					fprintf(stderr, "the compressed chunk at offset %lu has no readable length\n", at);
-					return SNAPPY_INVALID_INPUT;
-				}
-			}
-			if (n > 65536) {
-				fprintf(stderr, "the chunk at offset %lu holds more than 65536 bytes\n", at);
-				return SNAPPY_INVALID_INPUT;
-			}
-			*total += n;
-		} else if (type < 0x80) {
-			fprintf(stderr, "reserved unskippable chunk 0x%02x at offset %lu\n", type, at);
-			return SNAPPY_INVALID_INPUT;
-		}
+		*total += n;
 		at += 4ul + L;
 	}
 	if (!identified) {
@@ -529,6 +543,81 @@ snappy_status snappy_decompress_sz_host(struct host_buffer_context *input, struc
 	output->buffer = out;
 	output->curr = op;
 	output->length = (unsigned long)total;
+	return SNAPPY_OK;
+}
+
+/* Bytes [offset, offset + length) of the plaintext of a .sz file, by the rules of snappy_hip_sz_decompress_ranges: the chain is
+ * walked only up to the last chunk the range touches, and only the touched chunks -- chunk k with dst_off[k] <= offset + length - 1
+ * and dst_off[k] + n[k] > offset, which are the device's first..last -- are decoded, in full, and their CRCs compared unless
+ * no_verify.  A chain broken before the range ends, a range beyond the plaintext, a touched chunk that does not decode or fails
+ * its CRC (named on stderr): SNAPPY_INVALID_INPUT, no output.  A bad chunk the range does not touch is never looked at. */
+snappy_status snappy_decompress_sz_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,
+                                              uint64_t length, int no_verify)
+{
+	const uint8_t *buf = input->buffer;
+	const unsigned long len = input->length;
+	const uint64_t end = offset + length;
+	output->buffer = NULL;
+	output->length = 0;
+	if (end < offset) {
+		fprintf(stderr, "the range [%llu, +%llu) overflows\n", (unsigned long long)offset, (unsigned long long)length);
+		return SNAPPY_INVALID_INPUT;
+	}
+	if (length > output->max)
+		return SNAPPY_BUFFER_TOO_SMALL;
+	uint8_t *out = malloc(length ? length : 1), *piece = malloc(65536);
+	snappy_status st = (out && piece) ? SNAPPY_OK : SNAPPY_BUFFER_TOO_SMALL;
+	unsigned long at = 0, k = 0;
+	uint64_t total = 0;                                      /* the plaintext in front of the chunk at `at` */
+	int identified = 0;
+	while (st == SNAPPY_OK && at < len && !(identified && total >= end)) {
+		uint32_t type, L, n;
+		if ((st = sz_chunk_host(buf, len, at, &identified, &type, &L, &n)) != SNAPPY_OK)
+			break;
+		if (type <= 1) {
+			const uint8_t *body = buf + at + 4;
+			if (length && total < end && total + n > offset) {               /* touched */
+				if (type == 0) {
+					uint32_t stated;
+					const uint8_t *ip = varint_get(body + 4, body + L, &stated);
+					if (decompress_block_host(ip, body + L, piece, piece, piece + n) != piece + n) {
+						fprintf(stderr, "data chunk %lu at offset %lu does not decode\n", k, at);
+						st = SNAPPY_INVALID_INPUT;
+						break;
+					}
+				} else {
+					memcpy(piece, body + 4, n);
+				}
+				if (!no_verify && crc_mask_host(crc32c_host(piece, n)) != load32(body)) {
+					fprintf(stderr, "data chunk %lu at offset %lu fails its CRC-32C\n", k, at);
+					st = SNAPPY_INVALID_INPUT;
+					break;
+				}
+				const uint64_t from = offset > total ? offset : total, to = end < total + n ? end : total + n;
+				memcpy(out + (from - offset), piece + (from - total), to - from);
+			}
+			total += n;
+			k++;
+		}
+		at += 4ul + L;
+	}
+	if (st == SNAPPY_OK && !identified) {
+		fprintf(stderr, "no stream identifier\n");
+		st = SNAPPY_INVALID_INPUT;
+	}
+	if (st == SNAPPY_OK && total < end) {
+		fprintf(stderr, "the range [%llu, %llu) lies beyond the plaintext of %llu bytes\n", (unsigned long long)offset, (unsigned long long)end,
+		        (unsigned long long)total);
+		st = SNAPPY_INVALID_INPUT;
+	}
+	free(piece);
+	if (st != SNAPPY_OK) {
+		free(out);
+		return st;
+	}
+	output->buffer = out;
+	output->curr = out + length;
+	output->length = (unsigned long)length;
 	return SNAPPY_OK;
 }
 

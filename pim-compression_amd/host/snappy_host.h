@@ -44,6 +44,10 @@ snappy_status snappy_check_raw_host(const struct host_buffer_context *input, uin
  * by the device's rules, and compares every chunk's CRC-32C unless no_verify.  Both malloc output->buffer. */
 snappy_status snappy_compress_sz_host(struct host_buffer_context *input, struct host_buffer_context *output, uint32_t chunk_len);
 snappy_status snappy_decompress_sz_host(struct host_buffer_context *input, struct host_buffer_context *output, int no_verify);
+/* dpu_snappy -z -x: bytes [offset, offset + length) of a .sz file's plaintext; only the chunks the range touches are decoded and
+ * judged, as snappy_hip_sz_decompress_ranges judges them.  mallocs output->buffer. */
+snappy_status snappy_decompress_sz_range_host(struct host_buffer_context *input, struct host_buffer_context *output, uint64_t offset,
+                                              uint64_t length, int no_verify);
 double get_runtime(struct timeval *start, struct timeval *end);
 
 #ifdef __cplusplus

@@ -146,6 +146,14 @@ def lib():
         L.snappy_hip_sz_decompress_split_scratch_bytes.argtypes = [u32, u32, u32, u64]
         L.snappy_hip_sz_decompress_split_batch.restype = ctypes.c_int
         L.snappy_hip_sz_decompress_split_batch.argtypes = [vp, u32, u32, u32, u64, u32, vp, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_sz_index_scratch_bytes.restype = u64
+        L.snappy_hip_sz_index_scratch_bytes.argtypes = [u32, u32, u32, u64]
+        L.snappy_hip_sz_index_batch.restype = ctypes.c_int
+        L.snappy_hip_sz_index_batch.argtypes = [vp, u32, u32, u32, u64, vp, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_sz_decompress_ranges_scratch_bytes.restype = u64
+        L.snappy_hip_sz_decompress_ranges_scratch_bytes.argtypes = [u32]
+        L.snappy_hip_sz_decompress_ranges.restype = ctypes.c_int
+        L.snappy_hip_sz_decompress_ranges.argtypes = [vp, u32, vp, u32, u32, vp, vp, vp, u64, vp]
         L.snappy_hip_sz_compress_bound.restype = u64
         L.snappy_hip_sz_compress_bound.argtypes = [u64, u32]
         L.snappy_hip_sz_compress_scratch_bytes.restype = u64
@@ -158,6 +166,9 @@ def lib():
         L.snappy_decompress_sz_gpu.restype = ctypes.c_int
         L.snappy_decompress_sz_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
                                                ctypes.POINTER(ProgramRuntime)]
+        L.snappy_decompress_sz_range_gpu.restype = ctypes.c_int
+        L.snappy_decompress_sz_range_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u64, u64, u32,
+                                                     ctypes.POINTER(ProgramRuntime)]
         L.snappy_decompress_sz_split_gpu.restype = ctypes.c_int
         L.snappy_decompress_sz_split_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
                                                      ctypes.POINTER(ProgramRuntime)]
@@ -671,6 +682,52 @@ def sz_decompress_split_batch(d_items, count, max_chunks, segment_bytes, max_seg
     return d_scratch
 
 
+# byte ranges of .sz streams from a resident chunk index (snappy_hip_sz_index_batch / snappy_hip_sz_decompress_ranges)
+SZ_CHUNK_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("info", "<u4"), ("ulen", "<u4"), ("item", "<u4"), ("reserved", "<u4")])   # snappy_hip_sz_chunk
+SZ_DESC_DTYPE = np.dtype([("src", "<u8"), ("src_len", "<u8"), ("chunks", "<u8"), ("num_chunks", "<u8"), ("total_len", "<u8")])   # snappy_hip_sz_desc
+
+
+def sz_index_scratch_bytes(count, max_chunks, segment_bytes, max_segments):
+    """Scratch of snappy_hip_sz_index_batch (0 for a bad segment_bytes)."""
+    return int(lib().snappy_hip_sz_index_scratch_bytes(count, max_chunks, segment_bytes, max_segments))
+
+
+def sz_index_batch(d_items, count, max_chunks, segment_bytes, max_segments, d_chunks, d_descs, d_status, d_result, d_scratch=None):
+    """Enqueue snappy_hip_sz_index_batch on the current stream: the chunk index of `count` .sz streams.  d_items: make_raw_items()
+    tensor (dst and capacity are ignored); d_chunks: device uint8 tensor of 32 * max_chunks bytes (SZ_CHUNK_DTYPE), d_descs: of
+    40 * count bytes (SZ_DESC_DTYPE); d_status: device int32 tensor of `count`, d_result: of four.  d_scratch: 256-byte aligned
+    device uint8 tensor (default: a fresh one).  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(sz_index_scratch_bytes(count, max_chunks, segment_bytes, max_segments), 256), dtype=torch.uint8,
+                                device=d_result.device)
+    _check(lib().snappy_hip_sz_index_batch(d_items.data_ptr() if count else None, count, max_chunks, segment_bytes, max_segments,
+                                           d_chunks.data_ptr() if max_chunks else None, d_descs.data_ptr() if count else None,
+                                           d_status.data_ptr() if count else None, d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(),
+                                           _stream_handle(torch)), "snappy_hip_sz_index_batch")
+    return d_scratch
+
+
+def sz_decompress_ranges_scratch_bytes(range_count):
+    """Scratch for a full grid of snappy_hip_sz_decompress_ranges on the current device."""
+    return int(lib().snappy_hip_sz_decompress_ranges_scratch_bytes(range_count))
+
+
+def sz_decompress_ranges(d_descs, count, d_ranges, range_count, d_status, d_bad_chunk, flags=0, d_scratch=None):
+    """Enqueue snappy_hip_sz_decompress_ranges on the current stream.  d_descs: the tensor sz_index_batch filled (or any packed
+    SZ_DESC_DTYPE), d_ranges: make_ranges() tensor whose stream field indexes d_descs, d_status and d_bad_chunk: device int32
+    tensors of range_count entries.  flags: SZ_NO_VERIFY.  d_scratch: 256-byte aligned device uint8 tensor (default: a fresh one
+    for the full grid).  Nothing is synchronised."""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(sz_decompress_ranges_scratch_bytes(range_count), dtype=torch.uint8, device=d_status.device)
+    _check(lib().snappy_hip_sz_decompress_ranges(d_descs.data_ptr() if count else None, count, d_ranges.data_ptr() if range_count else None,
+                                                 range_count, flags, d_status.data_ptr() if range_count else None,
+                                                 d_bad_chunk.data_ptr() if range_count else None, d_scratch.data_ptr(), d_scratch.numel(),
+                                                 _stream_handle(torch)), "snappy_hip_sz_decompress_ranges")
+    return d_scratch
+
+
 def sz_compress_bound(src_len, chunk_len):
     """10 + 8 * chunks + src_len: a dst_capacity that always suffices, exact when nothing compresses (0 for a bad chunk_len)."""
     return int(lib().snappy_hip_sz_compress_bound(src_len, chunk_len))
@@ -973,3 +1030,8 @@ def check_raw_host(stream, split=False):
 def check_raw_split_host(stream):
     """snappy_check_raw_split_gpu on a whole raw Snappy stream held in host memory -> (status, uncompressed length, runtime dict)."""
     return check_raw_host(stream, split=True)
+
+
+def sz_decompress_range_host(stream, offset, length, flags=0, out_capacity=None):
+    """snappy_decompress_sz_range_gpu on a whole .sz stream held in host memory -> (status, the range's bytes, runtime dict)."""
+    return _raw_host(lambda i, o, r: lib().snappy_decompress_sz_range_gpu(i, o, offset, length, flags, r), stream, out_capacity)
