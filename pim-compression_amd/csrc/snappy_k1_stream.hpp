@@ -133,7 +133,8 @@ __device__ __forceinline__ void stream_issue_gather(StreamGather& g, const Table
 // checked, not assumed (a returned lane at or above the own one sends the window to the race tables of the bulk form).  The
 // lane returned is the nearest earlier lane in the same SLOT; if its hash is the same it is the nearest with the same HASH.
 // If it is not (an alias), the other table decides; a lane with an alias in front of it in both tables may have a partner
-// hidden behind them and is settled the long way (`cx`).  The tables are left zeroed.
+// hidden behind them: one ballot per such lane says whether any earlier lane has its hash, and only a lane that has one is
+// settled the long way (`cx`).  The tables are left zeroed.
 // ---------------------------------------------------------------------------
 #ifdef SNAPPY_EMU
 __device__ __forceinline__ uint32_t lds_max_rtn(lds_words_t p, uint32_t v)
@@ -193,6 +194,7 @@ __device__ __forceinline__ void stream_analyse(StreamDup& d, const StreamWindow&
     d = StreamDup();
     if (__ballot((oa && ja >= lane) || (ob && jb >= lane))) {    // not in lane order: the bulk form's race tables, every sharer a stop
         STREAM_STAT(7);
+        ALIAS_STAT(3);
         d.cx = dup_slot_lanes(scratch, w.h0, lane);
         for (uint32_t i = lane; i < 2u * kSlots; i += kWave) tab[i] = 0;   // the race tables live in the same bytes
         __builtin_amdgcn_wave_barrier();
@@ -206,6 +208,20 @@ __device__ __forceinline__ void stream_analyse(StreamDup& d, const StreamWindow&
     d.j1 = ma ? ja : jb;                                         // (meaningful in the lanes of nf)
     d.nf = MA | MB;
     d.cx = OA & OB & ~d.nf;
+    // Whether such a lane has an earlier lane with its hash at all does not depend on the parse: ask here, underneath the
+    // loads, and not on the walk.  Where there is none (an artefact of the tables' size, and the usual case) nothing of this
+    // window can change the lane's slot before it is probed: it is an ordinary lane, no stop, no partner of anybody's.
+    for (unsigned long long m = d.cx; m; m &= m - 1) {
+        const uint32_t s = (uint32_t)__builtin_ctzll(m);
+        const uint32_t hs = (uint32_t)__builtin_amdgcn_readlane((int)w.h0, (int)s);
+        ALIAS_STAT(0);
+        if (__ballot(w.h0 == hs) & ((1ull << s) - 1ull)) {
+            ALIAS_STAT(2);
+        } else {
+            ALIAS_STAT(1);
+            d.cx &= ~(1ull << s);
+        }
+    }
     if (d.nf) {
         const uint32_t jl = d.j1 & 63u;
         const uint32_t xj = (uint32_t)__shfl((int)w.a.x, (int)jl);
@@ -469,6 +485,13 @@ __device__ __forceinline__ void stream_run(const uint8_t* __restrict__ blk, uint
                     else if (dup.deep & bit_s) how = 2;          // a further lane of the chain may have been
                 }
                 if (dup.cx & bit_s) how = 2;
+#ifdef SNAPPY_EMU
+                if (dup.cx & bit_s) ALIAS_STAT(4);
+                else if (!(pend & bit_s)) ALIAS_STAT(8);
+                else if (how == 2) ALIAS_STAT(5);
+                else if (how == 1) ALIAS_STAT(7);
+                else ALIAS_STAT(6);
+#endif
                 // what the lane does: (advance, copy length) for the walk, (candidate, length - 4) for the emission, and
                 // whether the compared bytes all matched (the match may run on)
                 uint32_t adv_s, cl_s, cand_s = 0, sat_s = 24;
@@ -480,6 +503,7 @@ __device__ __forceinline__ void stream_run(const uint8_t* __restrict__ blk, uint
                     const uint32_t hs = (uint32_t)__builtin_amdgcn_readlane((int)cur.h0, (int)s);
                     const unsigned long long J = __ballot(cur.h0 == hs) & ins;
                     how = 0;
+                    if (!J) ALIAS_STAT(9);
                     if (J) {
                         j = 63u - (uint32_t)__builtin_clzll(J);
                         hit_s = (uint32_t)__builtin_amdgcn_readlane((int)cur.a.x, (int)s) == (uint32_t)__builtin_amdgcn_readlane((int)cur.a.x, (int)j);

@@ -333,8 +333,17 @@ __device__ __forceinline__ void emu_check_distinct_stores(bool, uint32_t, uint32
 // [15] not at all (64 misses)
 inline unsigned long long g_stream_stats[16] = {0};
 #define STREAM_STAT(i) do { if (lane == 0) ++g_stream_stats[i]; } while (0)
+// a second array, for the aliases of analyse()'s tables (snappy_k1_stream.hpp: stream_analyse) and for what the settles of the
+// stream form are caused by.  Lanes with an earlier lane in their slot in both tables, neither with their hash: [0] that
+// entered the loop that looks for an earlier lane with their hash, [1] cleared there (there is none), [2] kept (there is
+// one); [3] windows whose analysis fell back to the race tables (every sharer kept).  Settles by cause: [4] such a kept
+// lane, [5] a chain of three or more, [6] a partner that was not inserted, [7] a partner that was, [8] only that the
+// compared bytes all match; [9] settles with the ballot that found no inserted lane with the hash
+inline unsigned long long g_alias_stats[16] = {0};
+#define ALIAS_STAT(i) do { if (lane == 0) ++g_alias_stats[i]; } while (0)
 #else
 #define STREAM_STAT(i) ((void)0)
+#define ALIAS_STAT(i) ((void)0)
 #endif
 
 // TaggedGlobalTable behind a one-bit-per-slot "written in this block" filter in LDS (2 KiB per wavefront).  Early in a
