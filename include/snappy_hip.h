@@ -660,14 +660,40 @@ SNAPPY_HIP_API int snappy_hip_raw_check_split_batch(const snappy_hip_raw_item *d
  * u64 per item and, per fragment, a u32, a u64 and one compressed slot (snappy_hip_slot_stride).
  * The call only enqueues work on `stream`; the verdicts stay on the device.
  * SNAPPY_HIP_ERR_ARG (host side): null arrays with count > 0, a bad block size, a scratch that is misaligned or too small.
- * The fragments are compressed by K1's LDS-table form (as the update's dirty blocks are); a global-table variant for very
- * large batches is not part of this interface.
+ * The fragments are compressed by K1's LDS-table form (as the update's dirty blocks are); for very large batches
+ * snappy_hip_raw_compress_batch_tables (below) compresses them with K1's global-table wavefronts.
  */
 SNAPPY_HIP_API uint64_t snappy_hip_raw_compress_bound(uint64_t src_len, uint32_t block_size);
 SNAPPY_HIP_API uint64_t snappy_hip_raw_compress_scratch_bytes(uint32_t block_size, uint32_t count, uint32_t max_fragments);
 SNAPPY_HIP_API int snappy_hip_raw_compress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t block_size,
                                   uint32_t max_fragments, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result,
                                   void *d_scratch, uint64_t scratch_bytes, void *stream);
+
+/*
+ * snappy_hip_raw_compress_batch with the fragments compressed by K1's GLOBAL-table wavefronts (csrc/snappy_items_gt.hpp,
+ * DESIGN.md 3.15): the table of a wavefront lives in d_tables behind a filter (and, for block sizes above 8 KiB, a slot cache)
+ * in LDS, as in snappy_hip_compress_blocks, so a CU holds as many of them as it has wavefront slots where the LDS-table form
+ * fits about four at 32 KiB fragments.  The same items, parameters, d_scratch (snappy_hip_raw_compress_scratch_bytes) and
+ * results as the base call: every d_out_len[i], d_status[i], d_result[0], d_result[1] and every byte of every dst are
+ * identical, not one byte is written outside [dst, dst + dst_capacity), a DST_TOO_SMALL item keeps all of dst.  Only the time
+ * differs.
+ * d_result has FOUR words here, all always written by an accepted call: [0] and [1] as in the base call, [2] = the fragments
+ * that global-table wavefronts compressed, [3] = 0.
+ * d_tables: the 256-byte aligned workspace snappy_hip_compress_blocks takes; snappy_hip_compress_scratch_bytes() bytes give the
+ * full grid, fewer only mean fewer wavefronts (one 64 KiB table each behind a 256-byte head); room for one table is the least.
+ * Contents need not be initialised; it must not be shared with a launch that runs concurrently.
+ * The grid is the smallest of max_fragments, the global-table wavefronts the device holds, the tables of d_tables and
+ * SNAPPY_HIP_GT_WAVES when set (read per call).  A batch of no more fragments (max_fragments) than LDS-table wavefronts are
+ * resident at this block size -- the base call's grid -- runs the base call's fragment kernel, the few-blocks case being the
+ * LDS form's win, and d_result[2] = 0; SNAPPY_HIP_GT_WAVES set asks for global-table wavefronts whatever the size.
+ * The call only enqueues work on `stream` (one compress kernel, no helper stream); it never synchronises and never calls the
+ * allocator.  Opt-in, so refused, not ignored -- SNAPPY_HIP_ERR_ARG with nothing enqueued: a null, misaligned or too small
+ * d_tables, and each of the base call's own cases.
+ */
+SNAPPY_HIP_API int snappy_hip_raw_compress_batch_tables(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t block_size,
+                                         uint32_t max_fragments, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result,
+                                         void *d_scratch, uint64_t scratch_bytes, void *d_tables, uint64_t tables_bytes,
+                                         void *stream);
 
 /* ---- 1a'. the Snappy framing format (.sz) and CRC-32C on the device ------ */
 
@@ -783,6 +809,17 @@ SNAPPY_HIP_API uint64_t snappy_hip_sz_compress_scratch_bytes(uint32_t chunk_len,
 SNAPPY_HIP_API int snappy_hip_sz_compress_batch(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks,
                                  uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result, void *d_scratch,
                                  uint64_t scratch_bytes, void *stream);
+
+/*
+ * snappy_hip_sz_compress_batch with the chunks compressed by K1's global-table wavefronts: what
+ * snappy_hip_raw_compress_batch_tables is to snappy_hip_raw_compress_batch, with chunks for fragments -- identical outputs, a
+ * d_result of four words ([2] = the chunks that global-table wavefronts compressed, [3] = 0), the same d_tables, grid,
+ * small-batch rule and refusals.  The CRC, sizes and gather kernels are the base call's.
+ */
+SNAPPY_HIP_API int snappy_hip_sz_compress_batch_tables(const snappy_hip_raw_item *d_items, uint32_t count, uint32_t chunk_len,
+                                        uint32_t max_chunks, uint64_t *d_out_len, uint32_t *d_status, uint32_t *d_result,
+                                        void *d_scratch, uint64_t scratch_bytes, void *d_tables, uint64_t tables_bytes,
+                                        void *stream);
 
 /* ---- 1a''. byte ranges of .sz streams from a resident chunk index -------- */
 
@@ -921,6 +958,13 @@ SNAPPY_HIP_API snappy_status snappy_compress_raw_gpu(struct host_buffer_context 
                                       uint32_t block_size, struct program_runtime *runtime);
 
 /*
+ * snappy_compress_raw_gpu through snappy_hip_raw_compress_batch_tables (1a): the same output, byte for byte; the table
+ * workspace (snappy_hip_compress_scratch_bytes()) is allocated and freed by the call.
+ */
+SNAPPY_HIP_API snappy_status snappy_compress_raw_tables_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                             uint32_t block_size, struct program_runtime *runtime);
+
+/*
  * The raw Snappy stream in input (the whole file: input->buffer at its first byte, input->length = file size; from any
  * compressor) decoded to output (realloc'd to the header's length, or used as is when output->max is finite,
  * SNAPPY_BUFFER_TOO_SMALL if it does not fit).  One item through snappy_hip_raw_decompress_batch on the current device: ONE
@@ -951,6 +995,13 @@ SNAPPY_HIP_API snappy_status snappy_decompress_raw_split_gpu(struct host_buffer_
  */
 SNAPPY_HIP_API snappy_status snappy_compress_sz_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
                                      uint32_t chunk_len, struct program_runtime *runtime);
+
+/*
+ * snappy_compress_sz_gpu through snappy_hip_sz_compress_batch_tables (1a'): the same output, byte for byte; the table
+ * workspace (snappy_hip_compress_scratch_bytes()) is allocated and freed by the call.
+ */
+SNAPPY_HIP_API snappy_status snappy_compress_sz_tables_gpu(struct host_buffer_context *input, struct host_buffer_context *output,
+                                            uint32_t chunk_len, struct program_runtime *runtime);
 
 /*
  * The .sz stream in input (the whole file, from any writer) decoded to output (realloc'd to the plaintext's length, or used as

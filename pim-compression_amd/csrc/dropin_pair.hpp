@@ -1014,9 +1014,10 @@ struct RawVerdict {            // what one item's call leaves on the device
 };
 
 // compress = true: plaintext -> raw stream at `block_size` fragments; false: raw stream -> plaintext, by one wavefront, or --
-// split_unit >= 0 -- by snappy_hip_raw_decompress_split_batch at that unit_len (0 = its default), limits sized from the file
+// split_unit >= 0 -- by snappy_hip_raw_decompress_split_batch at that unit_len (0 = its default), limits sized from the file.
+// tables (compress): through snappy_hip_raw_compress_batch_tables with a table workspace of the full grid.
 snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
-                           struct program_runtime* runtime, int64_t split_unit = -1)
+                           struct program_runtime* runtime, int64_t split_unit = -1, bool tables = false)
 {
     if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
     PhasedCall call(runtime);
@@ -1055,17 +1056,20 @@ snappy_status raw_gpu_body(bool compress, struct host_buffer_context* input, str
     place(output, 0);
     if (snappy_status st = call.need_device()) return st;
 
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_tables = nullptr;
     snappy_hip_raw_item* d_item = nullptr;
     RawVerdict* d_verdict = nullptr;
+    const uint64_t tables_bytes = tables ? snappy_hip_compress_scratch_bytes() : 0;
     if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_out, capacity}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict},
-                                         {&d_scratch, scratch_bytes}}))
+                                         {&d_scratch, scratch_bytes}, {&d_tables, tables_bytes}}))
         return st;
     const snappy_hip_raw_item item{d_in, in_len, d_out, capacity};
     if (snappy_status st = call.upload({{d_in, input->buffer, in_len}, {d_item, &item, sizeof item}})) return st;
     if (snappy_status st = call.launch("raw batch", [&] {
-            return compress ? snappy_hip_raw_compress_batch(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
-                                                            d_verdict->result, d_scratch, scratch_bytes, nullptr)
+            return tables ? snappy_hip_raw_compress_batch_tables(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
+                                                                 d_verdict->result, d_scratch, scratch_bytes, d_tables, tables_bytes, nullptr)
+                   : compress ? snappy_hip_raw_compress_batch(d_item, 1, block_size, fragments, &d_verdict->out_len, &d_verdict->status,
+                                                              d_verdict->result, d_scratch, scratch_bytes, nullptr)
                    : split_unit >= 0
                        ? snappy_hip_raw_decompress_split_batch(d_item, 1, unit_len, 0, segments, units, &d_verdict->out_len, &d_verdict->status,
                                                                d_verdict->result, d_scratch, scratch_bytes, nullptr)
@@ -1132,8 +1136,9 @@ inline const char* sz_host_walk(const uint8_t* s, uint64_t len, uint64_t* chunks
 
 // compress = true: plaintext -> .sz at chunk_len; false: .sz -> plaintext, every CRC compared unless flags says not to.
 // split: the decode goes through snappy_hip_sz_decompress_split_batch at its default segment with a limit sized from the file.
+// tables (compress): through snappy_hip_sz_compress_batch_tables with a table workspace of the full grid.
 snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, struct host_buffer_context* output, uint32_t chunk_len, uint32_t flags,
-                          struct program_runtime* runtime, bool split = false)
+                          struct program_runtime* runtime, bool split = false, bool tables = false)
 {
     if (!input || !output || !runtime || (!input->buffer && input->length)) return SNAPPY_INVALID_INPUT;
     PhasedCall call(runtime);
@@ -1165,16 +1170,19 @@ snappy_status sz_gpu_body(bool compress, struct host_buffer_context* input, stru
     place(output, 0);
     if (snappy_status st = call.need_device()) return st;
 
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_tables = nullptr;
     snappy_hip_raw_item* d_item = nullptr;
     SzVerdict* d_verdict = nullptr;
+    const uint64_t tables_bytes = tables ? snappy_hip_compress_scratch_bytes() : 0;
     if (snappy_status st = call.buffers({{&d_in, in_len}, {&d_out, capacity}, {&d_item, sizeof *d_item}, {&d_verdict, sizeof *d_verdict},
-                                         {&d_scratch, scratch_bytes}}))
+                                         {&d_scratch, scratch_bytes}, {&d_tables, tables_bytes}}))
         return st;
     const snappy_hip_raw_item item{d_in, in_len, d_out, capacity};
     if (snappy_status st = call.upload({{d_in, input->buffer, in_len}, {d_item, &item, sizeof item}})) return st;
     if (snappy_status st = call.launch("sz batch", [&] {
-            return compress ? snappy_hip_sz_compress_batch(d_item, 1, chunk_len, (uint32_t)chunks, &d_verdict->out_len, &d_verdict->status,
+            return tables   ? snappy_hip_sz_compress_batch_tables(d_item, 1, chunk_len, (uint32_t)chunks, &d_verdict->out_len, &d_verdict->status,
+                                                                  d_verdict->result, d_scratch, scratch_bytes, d_tables, tables_bytes, nullptr)
+                   : compress ? snappy_hip_sz_compress_batch(d_item, 1, chunk_len, (uint32_t)chunks, &d_verdict->out_len, &d_verdict->status,
                                                            d_verdict->result, d_scratch, scratch_bytes, nullptr)
                    : split  ? snappy_hip_sz_decompress_split_batch(d_item, 1, (uint32_t)chunks, 0, segments, flags, &d_verdict->out_len,
                                                                    &d_verdict->status, &d_verdict->bad_chunk, d_verdict->result, d_scratch,
@@ -1494,6 +1502,12 @@ snappy_status snappy_compress_raw_gpu(struct host_buffer_context* input, struct 
     return entry_guard([&] { return raw_gpu_body(true, input, output, block_size, runtime); });
 }
 
+snappy_status snappy_compress_raw_tables_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t block_size,
+                                             struct program_runtime* runtime)
+{
+    return entry_guard([&] { return raw_gpu_body(true, input, output, block_size, runtime, -1, true); });
+}
+
 snappy_status snappy_decompress_raw_gpu(struct host_buffer_context* input, struct host_buffer_context* output, struct program_runtime* runtime)
 {
     return entry_guard([&] { return raw_gpu_body(false, input, output, 0, runtime); });
@@ -1509,6 +1523,12 @@ snappy_status snappy_compress_sz_gpu(struct host_buffer_context* input, struct h
                                      struct program_runtime* runtime)
 {
     return entry_guard([&] { return sz_gpu_body(true, input, output, chunk_len, 0, runtime); });
+}
+
+snappy_status snappy_compress_sz_tables_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t chunk_len,
+                                            struct program_runtime* runtime)
+{
+    return entry_guard([&] { return sz_gpu_body(true, input, output, chunk_len, 0, runtime, false, true); });
 }
 
 snappy_status snappy_decompress_sz_gpu(struct host_buffer_context* input, struct host_buffer_context* output, uint32_t flags,

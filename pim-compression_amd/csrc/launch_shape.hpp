@@ -111,4 +111,36 @@ inline uint32_t update_resident_waves(const DeviceShape& d, uint32_t wave_lds_by
     return std::max(1u, per_cu) * d.cus;
 }
 
+// The raw / .sz compress calls that take a table workspace (snappy_hip_raw_compress_batch_tables, ..._sz_...): one kernel of
+// global-table wavefronts, no LDS-table kernel beside it.
+// tables the workspace holds behind its 256-byte head (one 64 KiB table per wavefront, the stride of compress_scratch_bytes)
+inline uint64_t items_gt_tables(uint64_t tables_bytes)
+{
+    return tables_bytes > 256 ? (tables_bytes - 256) / ((uint64_t)kMaxTableEntries * sizeof(uint32_t)) : 0;
+}
+// global-table wavefronts the device holds at once when no LDS-table kernel runs beside them (k.gt_wave_bytes of LDS each)
+inline uint32_t gt_wave_budget(const DeviceShape& d, const K1Knobs& k)
+{
+    K1Knobs alone = k;
+    alone.lds_waves_forced = 0;
+    alone.waves_forced = -1;
+    return k1_default_launch(d, alone, ~0ull).gt_waves;
+}
+// A batch of no more fragments than LDS-table wavefronts are resident (k.lds_wave_bytes of LDS each; the grid of the base
+// calls' fragment kernel) is the LDS form's win, as a small container is (small_input_takes_lds_kernel_alone): the base call's
+// kernel takes it.  SNAPPY_HIP_GT_WAVES (k.waves_forced > 0) asks for global-table wavefronts and gets them.
+inline bool items_gt_small_batch(const DeviceShape& d, const K1Knobs& k, uint32_t max_fragments)
+{
+    return k.waves_forced <= 0 && max_fragments <= update_resident_waves(d, k.lds_wave_bytes);
+}
+// The grid: the smallest of max_fragments, the wave budget, the tables of the workspace and SNAPPY_HIP_GT_WAVES when set.
+// 0 = nothing to launch (no fragment, or no table).
+inline uint32_t items_gt_grid(const DeviceShape& d, const K1Knobs& k, uint32_t max_fragments, uint64_t tables_bytes)
+{
+    uint64_t grid = std::min<uint64_t>(max_fragments, gt_wave_budget(d, k));
+    grid = std::min(grid, items_gt_tables(tables_bytes));
+    if (k.waves_forced > 0) grid = std::min<uint64_t>(grid, (uint64_t)k.waves_forced);
+    return (uint32_t)grid;
+}
+
 }  // namespace launch_shape

@@ -297,6 +297,17 @@ uint32_t default_lds_waves_per_cu(uint32_t block_size)
     return launch_shape::default_lds_waves_per_cu(device_shape(), k);
 }
 
+// static LDS of one global-table wavefront at this block size: the filter (2 KiB), the scratch of the parse in its form and,
+// for blocks with full-size tables, the slot cache
+uint32_t global_table_wave_bytes(uint32_t block_size)
+{
+    const int k1_stream = k1_stream_forms(block_size);
+    const int gt_cache = gt_cache_slots(block_size);
+    return gt_cache ? ((k1_stream & 2) ? 4u << 10 : 3u << 10) + 4u * (uint32_t)gt_cache
+           : (k1_stream & 2) ? (2u << 10) + snappy_hip::stream_scratch_bytes(snappy_hip::kStreamSlotsGlobal)
+                             : 3u << 10;
+}
+
 // Number of shards the drop-in pair splits a file into: SNAPPY_HIP_NUM_GPUS (default: every visible device).
 // SNAPPY_HIP_OVERSUBSCRIBE=1 (test hook) allows more shards than devices; shard g then runs on device
 // (base + g) % device_count, so the sharding and host-side concat paths can be exercised on a one-GPU box.
@@ -568,14 +579,10 @@ static int launch_compress(const snappy_hip::K1Batch& w, uint32_t block_size, ui
     uint32_t* counter = static_cast<uint32_t*>(d_scratch);
     uint32_t* tables = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_scratch) + 256);
     HIP_TRY(hipMemsetAsync(counter, 0, 32, st));   // [0] next block, [4] blocks compressed by wavefronts with an LDS table
-    const int k1_stream = k1_stream_forms(block_size);
-    const int gt_cache = gt_cache_slots(block_size);
     launch_shape::K1Knobs knobs;
-    knobs.cached_global_table = gt_cache != 0;
+    knobs.cached_global_table = gt_cache_slots(block_size) != 0;
     knobs.lds_wave_bytes = lds_table_wave_bytes(block_size);
-    knobs.gt_wave_bytes = gt_cache ? ((k1_stream & 2) ? 4u << 10 : 3u << 10) + 4u * (uint32_t)gt_cache
-                          : (k1_stream & 2) ? (2u << 10) + snappy_hip::stream_scratch_bytes(snappy_hip::kStreamSlotsGlobal)
-                                            : 3u << 10;
+    knobs.gt_wave_bytes = global_table_wave_bytes(block_size);
     knobs.lds_waves_forced = env_int("SNAPPY_HIP_LDS_WAVES", -1);
     knobs.waves_forced = env_int("SNAPPY_HIP_GT_WAVES", -1);
     knobs.hybrid_min_blocks = (uint64_t)env_int("SNAPPY_HIP_HYBRID_MIN_BLOCKS", 4096);     // small inputs: one kernel is enough
@@ -865,6 +872,21 @@ uint32_t snappy_hip_host::range_grid_cap()
 int snappy_hip_host::check_k1_knobs() { return check_knobs(); }
 bool snappy_hip_host::lds_table_stream_form(uint32_t block_size) { return (k1_stream_forms(block_size) & 1) != 0; }
 uint32_t snappy_hip_host::lds_table_resident_waves(uint32_t lds_bytes) { return launch_shape::update_resident_waves(device_shape(), lds_bytes); }
+uint32_t snappy_hip_host::global_table_cache_slots(uint32_t block_size) { return (uint32_t)gt_cache_slots(block_size); }
+bool snappy_hip_host::global_table_stream_form(uint32_t block_size) { return (k1_stream_forms(block_size) & 2) != 0; }
+snappy_hip_host::ItemsGtLaunch snappy_hip_host::items_gt_launch(uint32_t block_size, uint32_t max_fragments, uint64_t tables_bytes)
+{
+    const launch_shape::DeviceShape shape = device_shape();
+    launch_shape::K1Knobs knobs;
+    knobs.cached_global_table = gt_cache_slots(block_size) != 0;
+    knobs.lds_wave_bytes = lds_table_wave_bytes(block_size);
+    knobs.gt_wave_bytes = global_table_wave_bytes(block_size);
+    knobs.waves_forced = env_int("SNAPPY_HIP_GT_WAVES", -1);
+    ItemsGtLaunch l;
+    l.small_batch = launch_shape::items_gt_small_batch(shape, knobs, max_fragments);
+    l.grid = launch_shape::items_gt_grid(shape, knobs, max_fragments, tables_bytes);
+    return l;
+}
 extern "C" {
 
 uint64_t snappy_hip_decompress_ranges_scratch_bytes(uint32_t max_block_size, uint32_t range_count)
@@ -1080,46 +1102,88 @@ int snappy_hip_raw_compress_batch(const snappy_hip_raw_item* d_items, uint32_t c
                                   uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch, uint64_t scratch_bytes,
                                   void* stream)
 {
+    if (int rc = raw_compress_check(d_items, count, block_size, max_fragments, d_out_len, d_status, d_result, d_scratch, scratch_bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = raw_compress_enqueue_plan(st, d_items, count, block_size, max_fragments, d_out_len, d_status, d_result, d_scratch)) return rc;
+    if (count && max_fragments)
+        if (int rc = raw_compress_enqueue_fragments(st, d_items, count, block_size, max_fragments, d_scratch)) return rc;
+    return raw_compress_enqueue_sizes_gather(st, d_items, count, block_size, max_fragments, d_out_len, d_status, d_result, d_scratch);
+}
+
+}  // extern "C"
+// (host_shared.hpp: the steps of the call above, shared with snappy_hip_items_gt.hip)
+namespace {
+struct RawCompressParts {
+    const snappy_hip::RawItem* items;
+    uint32_t stride;
+    snappy_hip::RawLayout l;
+    uint8_t* scratch;
+    uint32_t* ctl;
+    uint64_t* prefix;
+    uint32_t* frag_bytes;
+    uint64_t* place;
+    RawCompressParts(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t block_size, uint32_t max_fragments, void* d_scratch)
+        : items(reinterpret_cast<const snappy_hip::RawItem*>(d_items)), stride(snappy_hip_slot_stride(block_size)),
+          l(snappy_hip::raw_layout(count, max_fragments, stride)), scratch(static_cast<uint8_t*>(d_scratch)), ctl(reinterpret_cast<uint32_t*>(scratch)),
+          prefix(reinterpret_cast<uint64_t*>(scratch + l.prefix)), frag_bytes(reinterpret_cast<uint32_t*>(scratch + l.frag_bytes)),
+          place(reinterpret_cast<uint64_t*>(scratch + l.place))
+    {
+    }
+};
+}  // namespace
+snappy_hip_host::CompressParts snappy_hip_host::raw_compress_parts(uint32_t count, uint32_t block_size, uint32_t max_fragments, void* d_scratch)
+{
+    const RawCompressParts p(nullptr, count, block_size, max_fragments, d_scratch);
+    return CompressParts{p.ctl, p.prefix, p.frag_bytes, p.scratch + p.l.slots};
+}
+int snappy_hip_host::raw_compress_check(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t block_size, uint32_t max_fragments,
+                                        const uint64_t* d_out_len, const uint32_t* d_status, const uint32_t* d_result, const void* d_scratch,
+                                        uint64_t scratch_bytes)
+{
     if (!block_size_ok(block_size)) return fail(SNAPPY_HIP_ERR_ARG, "block_size must be 1..65535");
     if (!d_result || (count && (!d_items || !d_out_len || !d_status))) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
     if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
-    const uint32_t stride = snappy_hip_slot_stride(block_size);
-    const snappy_hip::RawLayout l = snappy_hip::raw_layout(count, max_fragments, stride);
+    const snappy_hip::RawLayout l = snappy_hip::raw_layout(count, max_fragments, snappy_hip_slot_stride(block_size));
     if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_raw_compress_scratch_bytes)");
-    if (int rc = check_knobs()) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
-    uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.prefix);
-    uint32_t* frag_bytes = reinterpret_cast<uint32_t*>(scratch + l.frag_bytes);
-    uint64_t* place = reinterpret_cast<uint64_t*>(scratch + l.place);
-    const auto* items = reinterpret_cast<const snappy_hip::RawItem*>(d_items);
-    hipLaunchKernelGGL(snappy_hip::raw_plan_kernel, dim3(1), dim3(1024), 0, st, items, count, block_size, max_fragments, d_out_len, d_status,
-                       d_result, ctl, prefix);
-    HIP_TRY(hipGetLastError());
-    if (count == 0 || max_fragments == 0) {
-        if (count)      // (no slot: only empty items can be OK)
-            hipLaunchKernelGGL(snappy_hip::raw_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, items, count, prefix, frag_bytes, place,
-                               d_out_len, d_status, d_result);
-        HIP_TRY(hipGetLastError());
-        return SNAPPY_HIP_OK;
-    }
-    const int rc = launch_counted(st, [&](uint32_t* counter) {
-        with_lds_table_form(block_size, [&](auto form, uint32_t lds) {
-            const uint32_t waves = std::min(launch_shape::update_resident_waves(device_shape(), lds), max_fragments);
-            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<form()>, dim3(waves), dim3(64), lds, st, items, count, block_size, ctl, prefix,
-                               frag_bytes, scratch + l.slots, stride, counter);
-        });
-        return 0;
-    });
-    if (rc) return rc;
-    hipLaunchKernelGGL(snappy_hip::raw_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, items, count, prefix, frag_bytes, place, d_out_len,
-                       d_status, d_result);
-    hipLaunchKernelGGL(snappy_hip::raw_gather_kernel, dim3(std::min(max_fragments, 32768u)), dim3(256), 0, st, items, count, ctl, prefix, frag_bytes,
-                       place, scratch + l.slots, stride, d_status);
+    return check_knobs();
+}
+int snappy_hip_host::raw_compress_enqueue_plan(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t block_size,
+                                               uint32_t max_fragments, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch)
+{
+    const RawCompressParts p(d_items, count, block_size, max_fragments, d_scratch);
+    hipLaunchKernelGGL(snappy_hip::raw_plan_kernel, dim3(1), dim3(1024), 0, st, p.items, count, block_size, max_fragments, d_out_len, d_status,
+                       d_result, p.ctl, p.prefix);
     HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
 }
+int snappy_hip_host::raw_compress_enqueue_fragments(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t block_size,
+                                                    uint32_t max_fragments, void* d_scratch)
+{
+    const RawCompressParts p(d_items, count, block_size, max_fragments, d_scratch);
+    return launch_counted(st, [&](uint32_t* counter) {
+        with_lds_table_form(block_size, [&](auto form, uint32_t lds) {
+            const uint32_t waves = std::min(launch_shape::update_resident_waves(device_shape(), lds), max_fragments);
+            hipLaunchKernelGGL(snappy_hip::raw_compress_fragments_kernel<form()>, dim3(waves), dim3(64), lds, st, p.items, count, block_size, p.ctl,
+                               p.prefix, p.frag_bytes, p.scratch + p.l.slots, p.stride, counter);
+        });
+        return 0;
+    });
+}
+int snappy_hip_host::raw_compress_enqueue_sizes_gather(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t block_size,
+                                                       uint32_t max_fragments, uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result,
+                                                       void* d_scratch)
+{
+    const RawCompressParts p(d_items, count, block_size, max_fragments, d_scratch);
+    if (count)      // (without a slot only empty items can be OK)
+        hipLaunchKernelGGL(snappy_hip::raw_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, p.items, count, p.prefix, p.frag_bytes, p.place,
+                           d_out_len, d_status, d_result);
+    if (count && max_fragments)
+        hipLaunchKernelGGL(snappy_hip::raw_gather_kernel, dim3(std::min(max_fragments, 32768u)), dim3(256), 0, st, p.items, count, p.ctl, p.prefix,
+                           p.frag_bytes, p.place, p.scratch + p.l.slots, p.stride, d_status);
+    HIP_TRY(hipGetLastError());
+    return SNAPPY_HIP_OK;
+}
+extern "C" {
 
 // ---- one large raw stream over many wavefronts (snappy_raw_split.hpp) ----
 static bool split_params(uint32_t& unit_len, uint32_t& segment_bytes)

@@ -141,56 +141,108 @@ uint64_t snappy_hip_sz_compress_scratch_bytes(uint32_t chunk_len, uint32_t count
 int snappy_hip_sz_compress_batch(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks, uint64_t* d_out_len,
                                  uint32_t* d_status, uint32_t* d_result, void* d_scratch, uint64_t scratch_bytes, void* stream)
 {
-    using namespace snappy_hip;
+    if (int rc = sz_compress_check(d_items, count, chunk_len, max_chunks, d_out_len, d_status, d_result, d_scratch, scratch_bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = sz_compress_enqueue_plan(st, d_items, count, chunk_len, max_chunks, d_out_len, d_status, d_result, d_scratch)) return rc;
+    if (count == 0) return SNAPPY_HIP_OK;
+    if (max_chunks)
+        if (int rc = sz_compress_enqueue_chunks(st, d_items, count, chunk_len, max_chunks, d_scratch)) return rc;
+    return sz_compress_enqueue_crc_sizes_gather(st, d_items, count, chunk_len, max_chunks, d_out_len, d_status, d_result, d_scratch);
+}
+
+}  // extern "C"
+
+// (host_shared.hpp: the steps of the call above, shared with snappy_hip_items_gt.hip)
+namespace {
+struct SzCompressParts {
+    const snappy_hip::RawItem* items;
+    uint32_t stride;
+    snappy_hip::SzCompressLayout l;
+    uint8_t* scratch;
+    uint32_t* ctl;
+    uint64_t* prefix;
+    uint32_t* frag_bytes;
+    uint64_t* place;
+    uint32_t* crc;
+    SzCompressParts(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks, void* d_scratch)
+        : items(reinterpret_cast<const snappy_hip::RawItem*>(d_items)), stride(snappy_hip_slot_stride(chunk_len)),
+          l(snappy_hip::sz_compress_layout(count, max_chunks, stride)), scratch(static_cast<uint8_t*>(d_scratch)), ctl(reinterpret_cast<uint32_t*>(scratch)),
+          prefix(reinterpret_cast<uint64_t*>(scratch + l.prefix)), frag_bytes(reinterpret_cast<uint32_t*>(scratch + l.frag_bytes)),
+          place(reinterpret_cast<uint64_t*>(scratch + l.place)), crc(reinterpret_cast<uint32_t*>(scratch + l.crc))
+    {
+    }
+};
+}  // namespace
+namespace snappy_hip_host {
+
+CompressParts sz_compress_parts(uint32_t count, uint32_t chunk_len, uint32_t max_chunks, void* d_scratch)
+{
+    const SzCompressParts p(nullptr, count, chunk_len, max_chunks, d_scratch);
+    return CompressParts{p.ctl, p.prefix, p.frag_bytes, p.scratch + p.l.slots};
+}
+
+int sz_compress_check(const snappy_hip_raw_item* d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks, const uint64_t* d_out_len,
+                      const uint32_t* d_status, const uint32_t* d_result, const void* d_scratch, uint64_t scratch_bytes)
+{
     if (!chunk_len_ok(chunk_len)) return fail(SNAPPY_HIP_ERR_ARG, "chunk_len must be 1..65535");
     if (!d_result || (count && (!d_items || !d_out_len || !d_status))) return fail(SNAPPY_HIP_ERR_ARG, "null device pointer");
     if (!d_scratch || ((uintptr_t)d_scratch & 255u)) return fail(SNAPPY_HIP_ERR_ARG, "d_scratch must be a 256-byte aligned device pointer");
-    const uint32_t stride = snappy_hip_slot_stride(chunk_len);
-    const SzCompressLayout l = sz_compress_layout(count, max_chunks, stride);
+    const snappy_hip::SzCompressLayout l = snappy_hip::sz_compress_layout(count, max_chunks, snappy_hip_slot_stride(chunk_len));
     if (scratch_bytes < l.total) return fail(SNAPPY_HIP_ERR_ARG, "scratch too small (snappy_hip_sz_compress_scratch_bytes)");
-    if (int rc = check_k1_knobs()) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* scratch = static_cast<uint8_t*>(d_scratch);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(scratch);
-    uint64_t* prefix = reinterpret_cast<uint64_t*>(scratch + l.prefix);
-    uint32_t* frag_bytes = reinterpret_cast<uint32_t*>(scratch + l.frag_bytes);
-    uint64_t* place = reinterpret_cast<uint64_t*>(scratch + l.place);
-    uint32_t* crc = reinterpret_cast<uint32_t*>(scratch + l.crc);
-    const auto* items = reinterpret_cast<const RawItem*>(d_items);
-    hipLaunchKernelGGL(sz_compress_plan_kernel, dim3(1), dim3(1024), 0, st, items, count, chunk_len, max_chunks, d_out_len, d_status, d_result, ctl,
-                       prefix);
-    HIP_TRY(hipGetLastError());
-    if (count == 0) return SNAPPY_HIP_OK;
-    const uint32_t item_grid = std::min(count, 4096u);
-    if (max_chunks) {
-        int rc = launch_counted(st, [&](uint32_t* counter) {
-            if (lds_table_stream_form(chunk_len)) {
-                const uint32_t lds = lds_table_stream_lds_bytes(chunk_len);
-                hipLaunchKernelGGL(sz_compress_chunks_kernel<3>, dim3(std::min(lds_table_resident_waves(lds), max_chunks)), dim3(64), lds, st, items,
-                                   count, chunk_len, ctl, prefix, frag_bytes, scratch + l.slots, stride, counter);
-            } else {
-                const uint32_t lds = lds_table_kernel_lds_bytes(chunk_len, true);
-                hipLaunchKernelGGL(sz_compress_chunks_kernel<2>, dim3(std::min(lds_table_resident_waves(lds), max_chunks)), dim3(64), lds, st, items,
-                                   count, chunk_len, ctl, prefix, frag_bytes, scratch + l.slots, stride, counter);
-            }
-            return 0;
-        });
-        if (rc) return rc;
-        rc = launch_counted(st, [&](uint32_t* counter) {
-            const uint32_t grid = std::min(range_grid_cap(), max_chunks);
-            if (crc_tables() == 4) hipLaunchKernelGGL(sz_chunk_crc_kernel<4>, dim3(grid), dim3(64), 0, st, items, count, chunk_len, ctl, prefix, crc, counter);
-            else hipLaunchKernelGGL(sz_chunk_crc_kernel<1>, dim3(grid), dim3(64), 0, st, items, count, chunk_len, ctl, prefix, crc, counter);
-            return 0;
-        });
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(sz_sizes_kernel, dim3(item_grid), dim3(64), 0, st, items, count, chunk_len, prefix, frag_bytes, place, d_out_len, d_status,
-                       d_result);
-    if (max_chunks)
-        hipLaunchKernelGGL(sz_gather_kernel, dim3(std::min(max_chunks, 32768u)), dim3(256), 0, st, items, count, chunk_len, ctl, prefix, frag_bytes,
-                           place, crc, scratch + l.slots, stride, d_status);
+    return check_k1_knobs();
+}
+
+int sz_compress_enqueue_plan(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks,
+                             uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch)
+{
+    const SzCompressParts p(d_items, count, chunk_len, max_chunks, d_scratch);
+    hipLaunchKernelGGL(snappy_hip::sz_compress_plan_kernel, dim3(1), dim3(1024), 0, st, p.items, count, chunk_len, max_chunks, d_out_len, d_status,
+                       d_result, p.ctl, p.prefix);
     HIP_TRY(hipGetLastError());
     return SNAPPY_HIP_OK;
 }
 
-}  // extern "C"
+int sz_compress_enqueue_chunks(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks,
+                               void* d_scratch)
+{
+    using namespace snappy_hip;
+    const SzCompressParts p(d_items, count, chunk_len, max_chunks, d_scratch);
+    return launch_counted(st, [&](uint32_t* counter) {
+        if (lds_table_stream_form(chunk_len)) {
+            const uint32_t lds = lds_table_stream_lds_bytes(chunk_len);
+            hipLaunchKernelGGL(sz_compress_chunks_kernel<3>, dim3(std::min(lds_table_resident_waves(lds), max_chunks)), dim3(64), lds, st, p.items,
+                               count, chunk_len, p.ctl, p.prefix, p.frag_bytes, p.scratch + p.l.slots, p.stride, counter);
+        } else {
+            const uint32_t lds = lds_table_kernel_lds_bytes(chunk_len, true);
+            hipLaunchKernelGGL(sz_compress_chunks_kernel<2>, dim3(std::min(lds_table_resident_waves(lds), max_chunks)), dim3(64), lds, st, p.items,
+                               count, chunk_len, p.ctl, p.prefix, p.frag_bytes, p.scratch + p.l.slots, p.stride, counter);
+        }
+        return 0;
+    });
+}
+
+int sz_compress_enqueue_crc_sizes_gather(hipStream_t st, const snappy_hip_raw_item* d_items, uint32_t count, uint32_t chunk_len, uint32_t max_chunks,
+                                         uint64_t* d_out_len, uint32_t* d_status, uint32_t* d_result, void* d_scratch)
+{
+    using namespace snappy_hip;
+    const SzCompressParts p(d_items, count, chunk_len, max_chunks, d_scratch);
+    if (count == 0) return SNAPPY_HIP_OK;
+    if (max_chunks) {
+        const int rc = launch_counted(st, [&](uint32_t* counter) {
+            const uint32_t grid = std::min(range_grid_cap(), max_chunks);
+            if (crc_tables() == 4) hipLaunchKernelGGL(sz_chunk_crc_kernel<4>, dim3(grid), dim3(64), 0, st, p.items, count, chunk_len, p.ctl, p.prefix, p.crc, counter);
+            else hipLaunchKernelGGL(sz_chunk_crc_kernel<1>, dim3(grid), dim3(64), 0, st, p.items, count, chunk_len, p.ctl, p.prefix, p.crc, counter);
+            return 0;
+        });
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(sz_sizes_kernel, dim3(std::min(count, 4096u)), dim3(64), 0, st, p.items, count, chunk_len, p.prefix, p.frag_bytes, p.place, d_out_len,
+                       d_status, d_result);
+    if (max_chunks)
+        hipLaunchKernelGGL(sz_gather_kernel, dim3(std::min(max_chunks, 32768u)), dim3(256), 0, st, p.items, count, chunk_len, p.ctl, p.prefix, p.frag_bytes,
+                           p.place, p.crc, p.scratch + p.l.slots, p.stride, d_status);
+    HIP_TRY(hipGetLastError());
+    return SNAPPY_HIP_OK;
+}
+
+}  // namespace snappy_hip_host

@@ -27,6 +27,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 #endif
 	fprintf(stderr, "Compress or decompress a file with Snappy\nCan use either the host CPU or MI355X GPUs\n");
 	fprintf(stderr, "usage: %s [-d] [-c] [-R] [-S [<unit_len>]] [-W [<waves>]] [-b <block_size>] [-g <gpus>] [-r <offset>:<length>] [-w <offset>:<patch_file>] [-t <keep_len>] [-a <tail_file>] -i <input_file> [-o <output_file>]\n", exe);
+	fprintf(stderr, "       %s -d -c -R|-z -G [-b <block_size>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] [-R [-S]] -T -i <input_file>\n", exe);
 	fprintf(stderr, "       %s [-d] [-c] -z [-S] [-b <chunk_len>] -i <input_file> [-o <output_file>]\n", exe);
 	fprintf(stderr, "       %s [-d] -z [-S] -T -i <input_file>\n", exe);
@@ -35,6 +36,7 @@ static void usage(const char *exe)                          /* dpu_snappy.c:70-8
 	fprintf(stderr, "c: perform compression, by default performs decompression\n");
 	fprintf(stderr, "R: the original (raw) Snappy format, varint(length) + one element stream, instead of the block-framed one\n");
 	fprintf(stderr, "z: the Snappy framing format (.sz, what snzip and the stream classes of other Snappy libraries write): chunks of <block_size> bytes, each with the CRC-32C of its plain bytes, which decompression compares; with -T: decode the file, compare every CRC, write nothing\n");
+	fprintf(stderr, "G: with -d -c and -R or -z: compress the fragments (chunks) with the global-table wavefronts of the block-framed compressor; the file written is the one without -G\n");
 	fprintf(stderr, "S: with -d -R, decompressing: decode one large raw stream with many wavefronts, in independent pieces of <unit_len> output bytes (default 65536; for a file of -c -R -b N: N or a multiple); a stream not built that way is decoded as without -S; with -d -R -T (no <unit_len>): check one large raw stream with many wavefronts, whatever built it; with -d -z (no <unit_len>), decompressing or with -T: walk the chunk chain of one large .sz stream with many wavefronts\n");
 	fprintf(stderr, "W: with -d, decompressing a block-framed file: put a workgroup of <waves> wavefronts (2, 4, 8 or 16, default 16) on every block instead of one wavefront; for small files\n");
 	fprintf(stderr, "b: block size used for compression, default is 32KB, ignored for decompression\n");
@@ -129,7 +131,8 @@ int main(int argc, char **argv)
 	int split_has_unit = 0;
 	int use_wide = 0;
 	unsigned long wide_waves = 0;
-	while ((opt = getopt(argc, argv, "dcRzTS::W::b:g:i:o:r:w:t:a:x:")) != -1) {
+	int use_tables = 0;
+	while ((opt = getopt(argc, argv, "dcRzGTS::W::b:g:i:o:r:w:t:a:x:")) != -1) {
 		switch (opt) {
 		case 'S': {                  /* -S, -S<unit_len> or -S <unit_len> */
 			const char *arg = optarg;
@@ -219,6 +222,7 @@ int main(int argc, char **argv)
 		case 'c': compress = 1; break;
 		case 'R': raw = 1; break;
 		case 'z': sz = 1; break;
+		case 'G': use_tables = 1; break;
 		case 'b': block_size = atoi(optarg); break;
 		case 'g': setenv("SNAPPY_HIP_NUM_GPUS", optarg, 1); break;
 		case 'i': in_path = optarg; break;
@@ -231,6 +235,10 @@ int main(int argc, char **argv)
 	if (!in_path) {
 		usage(argv[0]);
 		return -1;
+	}
+	if (use_tables && (!use_gpu || !compress || (!raw && !sz))) {
+		fprintf(stderr, "-G compresses one raw Snappy or .sz stream with global-table wavefronts: it goes with -d -c and one of -R and -z\n");
+		return -2;
 	}
 	if (use_range && compress) {
 		fprintf(stderr, "-r selects a range of a compressed file: it does not go with -c\n");
@@ -387,7 +395,8 @@ int main(int argc, char **argv)
 		output.curr = NULL;
 		output.max = ULONG_MAX;
 		if (use_gpu) {
-			st = compress    ? snappy_compress_sz_gpu(&input, &output, (uint32_t)block_size, &rt)
+			st = use_tables  ? snappy_compress_sz_tables_gpu(&input, &output, (uint32_t)block_size, &rt)
+			     : compress  ? snappy_compress_sz_gpu(&input, &output, (uint32_t)block_size, &rt)
 			     : use_split ? snappy_decompress_sz_split_gpu(&input, &output, 0, &rt)
 			                 : snappy_decompress_sz_gpu(&input, &output, 0, &rt);   /* (host mode ignores -S) */
 		} else {
@@ -403,7 +412,8 @@ int main(int argc, char **argv)
 			output.buffer = NULL;
 			output.curr = NULL;
 			output.max = ULONG_MAX;
-			st = compress    ? snappy_compress_raw_gpu(&input, &output, (uint32_t)block_size, &rt)
+			st = use_tables  ? snappy_compress_raw_tables_gpu(&input, &output, (uint32_t)block_size, &rt)
+			     : compress  ? snappy_compress_raw_gpu(&input, &output, (uint32_t)block_size, &rt)
 			     : use_split ? snappy_decompress_raw_split_gpu(&input, &output, (uint32_t)split_unit, &rt)
 			                 : snappy_decompress_raw_gpu(&input, &output, &rt);   /* (host mode ignores -S) */
 		} else {

@@ -136,6 +136,15 @@ def lib():
         L.snappy_hip_raw_compress_scratch_bytes.argtypes = [u32, u32, u32]
         L.snappy_hip_raw_compress_batch.restype = ctypes.c_int
         L.snappy_hip_raw_compress_batch.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp]
+        L.snappy_hip_raw_compress_batch_tables.restype = ctypes.c_int
+        L.snappy_hip_raw_compress_batch_tables.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp, u64, vp]
+        L.snappy_hip_sz_compress_batch_tables.restype = ctypes.c_int
+        L.snappy_hip_sz_compress_batch_tables.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp, u64, vp, u64, vp]
+        L.snappy_compress_raw_tables_gpu.restype = ctypes.c_int
+        L.snappy_compress_raw_tables_gpu.argtypes = [ctypes.POINTER(HostBufferContext), ctypes.POINTER(HostBufferContext), u32,
+                                                     ctypes.POINTER(ProgramRuntime)]
+        L.snappy_compress_sz_tables_gpu.restype = ctypes.c_int
+        L.snappy_compress_sz_tables_gpu.argtypes = L.snappy_compress_raw_tables_gpu.argtypes
         L.snappy_hip_crc32c_batch.restype = ctypes.c_int
         L.snappy_hip_crc32c_batch.argtypes = [vp, u32, vp, vp]
         L.snappy_hip_sz_decompress_scratch_bytes.restype = u64
@@ -616,6 +625,45 @@ def raw_compress_batch(d_items, count, block_size, max_fragments, d_out_len, d_s
     return d_scratch
 
 
+def compress_tables(device=None):
+    """A fresh table workspace of the full grid for raw_compress_batch_tables / sz_compress_batch_tables (and compress_blocks):
+    snappy_hip_compress_scratch_bytes() bytes, 256-byte aligned, not initialised."""
+    import torch
+    return torch.empty(int(lib().snappy_hip_compress_scratch_bytes()), dtype=torch.uint8, device=device or "cuda")
+
+
+def raw_compress_batch_tables(d_items, count, block_size, max_fragments, d_out_len, d_status, d_result, d_tables=None, d_scratch=None):
+    """Enqueue snappy_hip_raw_compress_batch_tables on the current stream: raw_compress_batch with the fragments compressed by
+    K1's global-table wavefronts.  Arrays as in raw_compress_batch, but d_result has FOUR int32 entries ([2] = the fragments
+    global-table wavefronts compressed, [3] = 0).  d_tables: 256-byte aligned device uint8 tensor (default: compress_tables());
+    fewer bytes only mean fewer wavefronts, less than one table is refused.  Nothing is synchronised.  -> (d_scratch, d_tables)"""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(raw_compress_scratch_bytes(block_size, count, max_fragments), 256), dtype=torch.uint8, device=d_result.device)
+    if d_tables is None:
+        d_tables = compress_tables(d_result.device)
+    _check(lib().snappy_hip_raw_compress_batch_tables(d_items.data_ptr() if count else None, count, block_size, max_fragments,
+                                                      d_out_len.data_ptr() if count else None, d_status.data_ptr() if count else None,
+                                                      d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(), d_tables.data_ptr(),
+                                                      d_tables.numel(), _stream_handle(torch)), "snappy_hip_raw_compress_batch_tables")
+    return d_scratch, d_tables
+
+
+def sz_compress_batch_tables(d_items, count, chunk_len, max_chunks, d_out_len, d_status, d_result, d_tables=None, d_scratch=None):
+    """Enqueue snappy_hip_sz_compress_batch_tables on the current stream: sz_compress_batch with the chunks compressed by K1's
+    global-table wavefronts.  Arrays and d_tables as in raw_compress_batch_tables.  -> (d_scratch, d_tables)"""
+    import torch
+    if d_scratch is None:
+        d_scratch = torch.empty(max(sz_compress_scratch_bytes(chunk_len, count, max_chunks), 256), dtype=torch.uint8, device=d_result.device)
+    if d_tables is None:
+        d_tables = compress_tables(d_result.device)
+    _check(lib().snappy_hip_sz_compress_batch_tables(d_items.data_ptr() if count else None, count, chunk_len, max_chunks,
+                                                     d_out_len.data_ptr() if count else None, d_status.data_ptr() if count else None,
+                                                     d_result.data_ptr(), d_scratch.data_ptr(), d_scratch.numel(), d_tables.data_ptr(),
+                                                     d_tables.numel(), _stream_handle(torch)), "snappy_hip_sz_compress_batch_tables")
+    return d_scratch, d_tables
+
+
 # the Snappy framing format (.sz) and CRC-32C (snappy_hip_sz_decompress_batch / snappy_hip_sz_compress_batch / snappy_hip_crc32c_batch)
 SZ_CRC_MISMATCH = 7
 SZ_UNSUPPORTED = 8
@@ -981,6 +1029,16 @@ def _raw_host(call, data, out_capacity):
 def raw_compress_host(data, block_size=32768, out_capacity=None):
     """snappy_compress_raw_gpu on a host buffer -> (status, raw Snappy stream, runtime dict).  out_capacity: as in compress_host."""
     return _raw_host(lambda i, o, r: lib().snappy_compress_raw_gpu(i, o, block_size, r), data, out_capacity)
+
+
+def raw_compress_tables_host(data, block_size=32768, out_capacity=None):
+    """snappy_compress_raw_tables_gpu on a host buffer -> (status, raw Snappy stream, runtime dict): raw_compress_host's bytes."""
+    return _raw_host(lambda i, o, r: lib().snappy_compress_raw_tables_gpu(i, o, block_size, r), data, out_capacity)
+
+
+def sz_compress_tables_host(data, chunk_len=32768, out_capacity=None):
+    """snappy_compress_sz_tables_gpu on a host buffer -> (status, .sz stream, runtime dict): sz_compress_host's bytes."""
+    return _raw_host(lambda i, o, r: lib().snappy_compress_sz_tables_gpu(i, o, chunk_len, r), data, out_capacity)
 
 
 def raw_decompress_host(stream, out_capacity=None):
