@@ -2024,6 +2024,9 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                                                    uint32_t out_len, lds_bytes_t stage)
 {
     const uint32_t lane = threadIdx.x;
+    // wave-uniform by contract, but a caller's `at` may come out of a vector load: in scalar registers the 64-bit arithmetic
+    // on src is done once per block, not per lane in front of every window load
+    at = (uint64_t)uni((uint32_t)at) | ((uint64_t)uni((uint32_t)(at >> 32)) << 32);
     uint32_t st = kBlockOk;
     uint32_t csz = 0;
     if constexpr (kRaw) {
@@ -2043,40 +2046,46 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
     uint64_t w0 = 0;
     WindowLoad next = {0, 64};  // prefetch of the following 64 bytes (W1), shift applied at use
     WindowLoad next2 = {0, 64}; // batch form: the 64 bytes after those, so that W1 has arrived when a literal runs on into it
-    bool have_window = false;
+    uint32_t have_window = 0;
     // batch form: a window wholly inside the stream (all but the last windows of a stream's last blocks) is a plain load at a
     // 32-bit offset from the block's first element; the others take window_issue()'s clamped address and tail shift
     const uint32_t avail32 = avail > 0xffffff00ull ? 0xffffff00u : (uint32_t)avail;
-    bool next_tail = true, next2_tail = true;
-    auto issue = [&](uint32_t base, bool& tail) -> WindowLoad {
+    uint32_t next_tail = 1, next2_tail = 1;                          // (words, not bools: one scalar register each, not a lane mask)
+    auto issue = [&](uint32_t base, uint32_t& tail) -> WindowLoad {
         WindowLoad r;
         if (base + 72u <= avail32) {
             r.raw = ld64(src + (base + lane));
             r.shift = 0;
-            tail = false;
+            tail = 0;
         } else {
             r = window_issue(src, (uint64_t)base + lane, avail);
-            tail = true;
+            tail = 1;
         }
         return r;
     };
-    while (st == kBlockOk && cp < csz) {                             // one iteration per 64-byte window
-        // the window registers rotate at the END of a window (see there); only the first window of a block and the one
-        // after a long literal load afresh: all three requests go out before the first is awaited
-        if (!have_window) {
-            g = cp & ~63u;
-            bool cur_tail;
-            const WindowLoad cur = issue(g, cur_tail);
-            next = issue(g + 64u, next_tail);
-            next2 = issue(g + 128u, next2_tail);
-            w0 = cur_tail ? window_value(cur) : cur.raw;
-            have_window = true;
-        }
-        uint32_t offv = 0;
-        const uint32_t wend = (csz < g + 64) ? csz : g + 64;
+    // INTERIOR windows: all 64 bytes belong to this block (g + 64 <= csz), and the window and the two prefetched behind it
+    // are plain loads (g + 128 + 72 <= avail32) -- exactly the bases below steady_end, a multiple of 64 (0: none).
+    uint32_t steady_end = 0;
+    if (csz >= 64u && avail32 >= 200u) {
+        const uint32_t a = csz - 64u, b = avail32 - 200u;
+        steady_end = ((a < b ? a : b) & ~63u) + 64u;
+    }
+    // One window's work, predecode to flush, for both loops below; false: the block is invalid (st says so; nothing of the
+    // window is stored), or the loop that called is to end.
+    // kSteady = false: the window at g, whatever it is; the registers rotate through issue() or are given up (have_window).
+    // kSteady = true: the window at g is interior and the window registers are plain loads -- no partial window, no tail
+    // shift.  They rotate unconditionally; true is returned when the NEXT window is interior too and follows at once, and
+    // only then its prefetch (a plain load) has been issued: next2 is for the caller to fill otherwise.
+    // The steady loop has this one shape -- straight through the window, the flush the same on every way, the one condition at
+    // its bottom -- because the compiler gives a loop with lane-dependent branches inside ONE latch whatever the source says:
+    // with the cold rotation on a way out of its own it moves that way into the loop, in front of the latch, and the loop
+    // carries the cold loop's registers (shifts, tail flags) again.
+    auto window = [&](auto steady_tag) __attribute__((always_inline)) -> bool {
+        constexpr bool kSteady = decltype(steady_tag)::value;
         {
+            uint32_t offv = 0;
             // ================= the whole window at once =================
-            const uint32_t wlim = wend - g;
+            const uint32_t wlim = kSteady ? 64u : ((csz < g + 64) ? csz : g + 64) - g;
             uint32_t e_type, e_hdr, e_len, e_consumed;
             unsigned long long REJ;
             predecode_window<kRaw>(w0, g + lane, csz, e_type, e_hdr, e_len, offv, e_consumed, REJ);
@@ -2108,20 +2117,17 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                     E |= __ballot(got != 0) & ~1ull;
                 }
             }
-            if (E & REJ) {                                           // an element predecode rejected
-                st = kBlockInvalid;
-                break;
-            }
+            // The window's validity is ONE scalar flag, tested once, in front of the window's first access to the output
+            // (the far copies' loads; nothing is stored before them): an element predecode rejected (its length, possibly
+            // nonsense, goes into the sums below -- they are not used then), the output overrun, a zero offset, a reach
+            // before the block's start, more than the stage holds.
             const uint32_t mylen = __builtin_amdgcn_inverse_ballot_w64(E) ? e_len : 0u;
             const uint32_t incl = wave_inclusive_scan(mylen, lane);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             const uint32_t rel = incl - mylen;                       // this lane's element inside the window's output
             const uint32_t dstp = op + rel;                          // ... and inside the block's
             const unsigned long long COPY = E & __ballot(e_type != 0);
-            if (op + total > out_len || (COPY & (__ballot(offv == 0) | __ballot(offv > dstp)))) {   // strict, cf. :167-173
-                st = kBlockInvalid;
-                break;
-            }
+            const unsigned long long BAD = (E & REJ) | (COPY & (__ballot(offv == 0) | __ballot(offv > dstp)));   // strict, cf. :167-173
             // ================= staged in LDS: the window's output is assembled in k2_stage and flushed once =================
             // Output bytes [op, op + staged) of this window live in stage[0, staged) until the flush; a back-reference into
             // them costs an LDS round trip instead of a trip to L2.  Only the part of a last literal that runs on beyond the
@@ -2138,9 +2144,10 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                 }
             }
             const uint32_t staged = total - (spills ? pe - (ps > 64u ? ps : 64u) : 0u);   // a tag in the last lanes: payload from ps > 64
-            if (staged > kK2StageBytes) {                            // cannot happen: 22 copies of 64 bytes are the most 64 bytes can hold
+            // (staged > kK2StageBytes cannot happen in a valid window: 22 copies of 64 bytes are the most 64 bytes can hold)
+            if ((BAD != 0) | (op + total > out_len) | (staged > kK2StageBytes)) {
                 st = kBlockInvalid;
-                break;
+                return false;
             }
             // ---- copies, first part.  "Steppable": does not overlap its own destination and is at least 4 bytes long, so ONE
             //      lane can do it in unaligned dword steps.  Far ones (source wholly before this window's output) load from
@@ -2177,7 +2184,7 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                 const uint32_t dbase = (uint32_t)__builtin_amdgcn_readlane((int)dstp, (int)le) - ps;   // byte at g + q goes to dbase + q
                 WindowLoad nx = next;
                 SNAPPY_PIN(nx.shift);                                // first use of the prefetch: wait here, not earlier
-                const uint64_t w1 = next_tail ? window_value(nx) : nx.raw;
+                const uint64_t w1 = (!kSteady && next_tail) ? window_value(nx) : nx.raw;
                 const uint32_t q = 64u + lane;
                 if (q >= ps && q < pe) win[dbase + q] = (uint8_t)w1;
                 if (pe > 128u) {
@@ -2213,6 +2220,10 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                 const uint32_t src_end = rel - offv + e_len;         // meaningful for near copies only
                 unsigned long long rem = COPY & ~FAR;
                 lds_bytes_t dp = stage + rel;
+                // (awaited on every path: waited for only where they are used, the two loads count as outstanding behind a
+                // window without far copies, and the wait moves to the head of the next window, where the flush is young)
+                SNAPPY_PIN(far_v0);
+                SNAPPY_PIN(far_v1);
                 if (is_far) {
                     lds_st32u(dp, far_v0);
                     lds_st32u(dp + far_o1, far_v1);
@@ -2277,11 +2288,22 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
             //      iteration makes the compiler copy a register an outstanding load will write; it then waits at the back
             //      edge for EVERY outstanding vector memory operation, vmcnt(0), the flush stores included -- a full write
             //      round trip per window.  Here the two prefetches are a window old, and only stores are in flight at the
-            //      back edge.)  After a literal that ran on beyond the next window the block loads afresh ----
+            //      back edge.)  After a literal that ran on beyond the next window the block loads afresh.
+            //      The steady loop stays while the next window is interior too (g + 64 < steady_end) and follows at once
+            //      (cp < g + 128; cp >= g + 64 behind a full window, so one compare says both): the plain rotation ----
             const uint32_t flush_at = op;
             op += total;
             cp = g + s;
-            if (cp < g + 128u) {
+            bool stay = false;
+            if constexpr (kSteady) {
+                stay = cp < (g + 128u < steady_end ? g + 128u : steady_end);
+                SNAPPY_PIN(next.raw);
+                SNAPPY_PIN(next2.raw);
+                w0 = next.raw;
+                next.raw = next2.raw;
+                g += 64;
+                if (stay) next2.raw = ld64(src + (g + 128u + lane));
+            } else if (cp < g + 128u) {
                 SNAPPY_PIN(next.raw);
                 SNAPPY_PIN(next2.raw);
                 w0 = next_tail ? window_value(next) : next.raw;
@@ -2290,7 +2312,7 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                 g += 64;
                 next2 = issue(g + 128u, next2_tail);
             } else {
-                have_window = false;
+                have_window = 0;
             }
             // ---- flush: stage[0, staged) -> the block's output at op, a dword per lane (the last one clamped back) ----
             if (staged >= 4u) {
@@ -2307,7 +2329,41 @@ __device__ __forceinline__ uint32_t k2_decode_block(const uint8_t* stream, uint6
                 win[flush_at + lane] = stage[lane];
             }
             __builtin_amdgcn_wave_barrier();
-            continue;
+            return stay;
+        }
+    };
+    // Two loops over the windows.  The COLD loop is the general one: it loads afresh (a block's first window, the one behind a
+    // literal that ran on beyond the prefetch), takes partial windows and the windows near a stream's end through
+    // window_issue()'s clamped address and tail shift.  As soon as the window it stands on is interior it hands over to the
+    // STEADY loop -- the registers it has loaded are plain loads then, nothing is reloaded -- which carries w0, next.raw,
+    // next2.raw and g alone and ends in front of the first window that is not interior or does not follow at once.
+    while (st == kBlockOk && cp < csz) {                             // one iteration per 64-byte window
+        // the window registers rotate at the END of a window (see there); only the first window of a block and the one
+        // after a long literal load afresh: all three requests go out before the first is awaited
+        if (!have_window) {
+            g = cp & ~63u;
+            uint32_t cur_tail;
+            const WindowLoad cur = issue(g, cur_tail);
+            next = issue(g + 64u, next_tail);
+            next2 = issue(g + 128u, next2_tail);
+            w0 = cur_tail ? window_value(cur) : cur.raw;
+            have_window = 1;
+        }
+        if (g < steady_end) {
+            next_tail = next2_tail = 0;                              // (what they are: g + 128 + 72 <= avail32)
+            next.shift = next2.shift = 0;
+#ifndef SNAPPY_EMU
+            // Nothing of the cold loop's is in flight inside the steady loop: a load still outstanding here counts as
+            // outstanding at the head of EVERY steady window for the compiler, which then waits there -- vmcnt(0), the
+            // flush stores of the window before included -- before it reuses that load's register.
+            __builtin_amdgcn_s_waitcnt(0);
+#endif
+            while (window(std::true_type{})) {}
+            // w0 and next are the plain loads at g and g + 64; next2 is missing
+            if (cp < g + 64u) next2 = issue(g + 128u, next2_tail);
+            else have_window = 0;
+        } else {
+            window(std::false_type{});
         }
     }
     if (st == kBlockOk && (op != out_len || cp != csz)) st = kBlockInvalid;

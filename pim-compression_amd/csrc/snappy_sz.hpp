@@ -215,8 +215,10 @@ __global__ __launch_bounds__(1024) void sz_plan_kernel(uint32_t count, uint32_t 
 }
 
 // Persistent wavefronts draw chunk numbers.  flags: kSzNoVerify skips the CRC.
+// amdgpu_num_sgpr: as on decompress_blocks_kernel (snappy_kernels.hpp) -- the 80 scalar registers this kernel took before
+// k2_decode_block had two window loops; it would take 81 now.
 template <int kTables>
-__global__ __launch_bounds__(64) void sz_decode_chunks_kernel(const RawItem* __restrict__ items, const uint32_t* __restrict__ ctl,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void sz_decode_chunks_kernel(const RawItem* __restrict__ items, const uint32_t* __restrict__ ctl,
                                                               SzChunk* __restrict__ chunks, uint32_t flags, uint32_t* next_chunk)
 {
     __shared__ __attribute__((aligned(16))) uint8_t stage_mem[kK2StageBytes];   // one window's output (K2's stage)

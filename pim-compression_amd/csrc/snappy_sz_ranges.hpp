@@ -180,8 +180,10 @@ __global__ __launch_bounds__(1024) void sz_range_pieces_kernel(const SzDesc* __r
     }
 }
 
+// amdgpu_num_sgpr: the most scalar registers at which the compiler still counts eight wavefronts per SIMD for this kernel.  With
+// the two window loops of k2_decode_block it would take 105; the ones beyond the cap live in lanes of a vector register.
 template <int kTables>
-__global__ __launch_bounds__(64) void sz_decompress_ranges_kernel(const SzDesc* __restrict__ descs, const RangeDesc* __restrict__ ranges,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(102))) void sz_decompress_ranges_kernel(const SzDesc* __restrict__ descs, const RangeDesc* __restrict__ ranges,
                                                                   uint32_t range_count, uint32_t flags, const uint64_t* __restrict__ prefix,
                                                                   const uint64_t* __restrict__ first_chunk, uint64_t* verdict,
                                                                   uint8_t* __restrict__ slots, uint32_t* next_piece)
